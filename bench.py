@@ -12,8 +12,14 @@ Prints ONE JSON line (rank 0). Extra objects:
   roofline      dominant kernel (conv3x3 MFMA-fp32 implicit GEMM, all 18 launches of a step):
                 algorithmic FLOPs / summed kernel time from HIP events recorded on the launch
                 stream during the timed steps, against the 157.3 TF fp32 matrix peak.
-  cpu_baseline  the CPU oracle (oracle/ref_cpu.py, stock torch CPU ops = the reference's CPU
-                path) on a bounded sample (rank 0, N = 1 only).
+  cpu_baseline  (--full only) the CPU oracle (oracle/ref_cpu.py, stock torch CPU ops = the
+                reference's CPU path) on a bounded sample (rank 0, N = 1 only).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line. Everything that takes a run of its own -- the CPU baselines of every mode, the eager
+per-kernel steps of the ae-train / ast-train modes -- is behind `--full`.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32): inputs
+and weights are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -48,7 +54,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--batch", type=int, default=None, help="images per GPU (config 2: 8, config 5: 32)")
     p.add_argument("--size", type=int, default=None, help="image side (config 2: 512, config 5: 1024)")
-    p.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline time budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline (fwd, train, "
+                        "mobilenet) and the eager per-kernel steps (ae-train, ast-train)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a "
+                        "fixed seeded sample of an output over the size limit)")
+    p.add_argument("--cpu-seconds", type=float, default=20.0,
+                   help="--full: CPU-baseline time budget (0 = skip)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="0 = best of os.cpu_count(), the affinity/cgroup CPU share and OMP_NUM_THREADS")
     p.add_argument("--mode", choices=["fwd", "train", "mobilenet", "ae-train", "ast-train"], default="fwd",
@@ -61,6 +74,26 @@ def parse():
                    help="mobilenet mode: stylise with the reference AST's AdaAttN (SURVEY §8f next #1) "
                         "instead of AdaIN")
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000   # all files of one --dump-outputs together (under 64 MB)
+
+
+def dump_outputs(path, outputs, rank=0, world=1):
+    """--dump-outputs: write the tensors of `outputs` (name -> what the timed path returned in its
+    last step) as <path>/<name>.npy in float32 (rank r > 0 of N: <name>.rank<r>.npy). The files
+    share DUMP_LIMIT_BYTES equally; an output over its share is written as a sample of its
+    flattened elements at fixed positions (numpy default_rng(0), sorted), the same in every run."""
+    import numpy as np
+    tensors = {k: v for k, v in outputs.items() if isinstance(v, torch.Tensor) and not k.startswith("_")}
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(tensors) * world) // 4
+    for name, t in tensors.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
 
 
 def train_bench(args, dev, rank, world):
@@ -94,6 +127,8 @@ def train_bench(args, dev, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out["loss"]), "non-finite loss"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     recs = timer.results()
     mm = [(tag, fl, ms) for tag, fl, ms in recs if tag.startswith(("conv3x3", "wgrad"))]
     fl = sum(f for _, f, _ in mm)
@@ -123,7 +158,7 @@ def train_bench(args, dev, rank, world):
                      "matrix_kernels_share_of_step": (ms + ms_gram) / args.steps / (elapsed / args.steps * 1e3),
                      "mfma_tflop_per_step": fl / args.steps / 1e12},
     }
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not args.full_losses:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and not args.full_losses:
         result["cpu_baseline"] = cpu_baseline_train(S, args.cpu_seconds, cpu_thread_options(args.cpu_threads))
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -158,22 +193,8 @@ def ae_train_bench(args, dev, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out["loss"]), "non-finite loss"
-    # per-kernel-family times: HIP events around every launch of further steps, outside the timed
-    # region (the eager step is host-issue-bound, so two events per launch would inflate it)
-    ksteps = 3
-    timer = ops.LaunchTimer()
-    with timer:
-        for _ in range(ksteps):
-            trainer.train_step(content, record=False)
-    torch.cuda.synchronize(dev)
-    fam = {}
-    for tag, fl, ms in timer.results():
-        k = tag.split()[0]
-        f0, m0, c0 = fam.get(k, (0.0, 0.0, 0))
-        fam[k] = (f0 + fl, m0 + ms, c0 + 1)
-    mm = [fam[k] for k in fam if k.startswith(("conv3x3", "wgrad"))]
-    fl, ms = sum(f for f, _, _ in mm), sum(m for _, m, _ in mm)
-    tf = fl / (ms * 1e-3) / 1e12 if ms else 0.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     result = {
         "metric": "AutoEncoder training images/sec (train_autoencoder.py step)",
         "value": B * world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -184,14 +205,33 @@ def ae_train_bench(args, dev, rank, world):
                                f"perceptual Huber via VGG relu_1..relu_15; clip 10 + Adam), bs={B}/GPU {S}x{S} fp32",
                    "global_batch": B * world, "image_size": S,
                    "parallelism": f"data-parallel x{world}" + (" + SyncBatchNorm" if world > 1 else "")},
-        "roofline": {"bound": "mfma", "kernel": "loss-network conv3x3 fwd/dgrad launches of a step (split-bf16)",
-                     "achieved": tf, "peak": PEAK_SPLIT_BF16_TF, "unit": "TFLOP/s", "frac": tf / PEAK_SPLIT_BF16_TF,
-                     "fp32_mfma_peak": PEAK_FP32_MFMA_TF, "frac_of_fp32_mfma_peak": tf / PEAK_FP32_MFMA_TF,
-                     "traffic": None, "mfma_share_of_step": ms / ksteps / (elapsed / args.steps * 1e3),
-                     "timing_source": "HIP events around each launch of 3 eager steps after the timed ones"},
-        "kernels_ms_per_step": {k: round(m / ksteps, 4) for k, (f, m, c) in sorted(fam.items())},
-        "mbgemm_tflops": (fam["mbgemm"][0] / (fam["mbgemm"][1] * 1e-3) / 1e12) if "mbgemm" in fam else None,
     }
+    if args.full:
+        # per-kernel-family times: HIP events around every launch of further steps, outside the timed
+        # region (the eager step is host-issue-bound, so two events per launch would inflate it)
+        ksteps = 3
+        timer = ops.LaunchTimer()
+        with timer:
+            for _ in range(ksteps):
+                trainer.train_step(content, record=False)
+        torch.cuda.synchronize(dev)
+        fam = {}
+        for tag, fl, ms in timer.results():
+            k = tag.split()[0]
+            f0, m0, c0 = fam.get(k, (0.0, 0.0, 0))
+            fam[k] = (f0 + fl, m0 + ms, c0 + 1)
+        mm = [fam[k] for k in fam if k.startswith(("conv3x3", "wgrad"))]
+        fl, ms = sum(f for f, _, _ in mm), sum(m for _, m, _ in mm)
+        tf = fl / (ms * 1e-3) / 1e12 if ms else 0.0
+        result.update({
+            "roofline": {"bound": "mfma", "kernel": "loss-network conv3x3 fwd/dgrad launches of a step (split-bf16)",
+                         "achieved": tf, "peak": PEAK_SPLIT_BF16_TF, "unit": "TFLOP/s", "frac": tf / PEAK_SPLIT_BF16_TF,
+                         "fp32_mfma_peak": PEAK_FP32_MFMA_TF, "frac_of_fp32_mfma_peak": tf / PEAK_FP32_MFMA_TF,
+                         "traffic": None, "mfma_share_of_step": ms / ksteps / (elapsed / args.steps * 1e3),
+                         "timing_source": "HIP events around each launch of 3 eager steps after the timed ones"},
+            "kernels_ms_per_step": {k: round(m / ksteps, 4) for k, (f, m, c) in sorted(fam.items())},
+            "mbgemm_tflops": (fam["mbgemm"][0] / (fam["mbgemm"][1] * 1e-3) / 1e12) if "mbgemm" in fam else None,
+        })
     if rank == 0:
         print(json.dumps(result), flush=True)
 
@@ -228,51 +268,55 @@ def ast_train_bench(args, dev, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out["loss"]), "non-finite loss"
-    # per-kernel-family times: HIP events around every launch of an eager step (a replayed graph
-    # launches nothing from Python), same kernels and shapes as the timed steps
-    eager = ASTTrainer(default_ast_args(batch_size=B * world), device=dev,
-                       ast=models.AST(attention=True).load_live_init(), graph=False)
-    ksteps = 3
-    eager.train_step(content, style, record=False)
-    torch.cuda.synchronize(dev)
-    timer = ops.LaunchTimer()
-    te = time.perf_counter()
-    with timer:
-        for _ in range(ksteps):
-            eager.train_step(content, style, record=False)
-    torch.cuda.synchronize(dev)
-    eager_ms = (time.perf_counter() - te) / ksteps * 1e3
-    del eager
-    fam = {}
-    for tag, fl, ms in timer.results():
-        k = tag.split()[0]
-        f0, m0, c0 = fam.get(k, (0.0, 0.0, 0))
-        fam[k] = (f0 + fl, m0 + ms, c0 + 1)
-    mm = [fam[k] for k in fam if k.startswith(("conv3x3", "wgrad"))]
-    fl, ms = sum(f for f, _, _ in mm), sum(m for _, m, _ in mm)
-    tf = fl / (ms * 1e-3) / 1e12 if ms else 0.0
-    args.steps, steps_timed = ksteps, args.steps   # the per-step kernel figures below are per eager step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     result = {
         "metric": "AST training images/sec (train.py ASTTrainer step, MobileNet AST + AdaAttN)",
-        "value": B * world * steps_timed / elapsed, "unit": "images/s", "n_gpus": world, "steps": steps_timed,
-        "warmup": args.warmup, "ms_per_step": elapsed / steps_timed * 1e3, "higher_is_better": True,
+        "value": B * world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32",
         "data": "synthetic (live-init weights, U[0,1) images), resident in HBM",
         "step_mode": "hipGraph replay (train.StepGraph)" if graph else "eager",
-        "eager_ms_per_step": eager_ms,
         "config": {"workload": f"ASTTrainer step (MobileNet AST + AdaAttN in train mode; content, style, lf, tv, hist, "
                                f"org_img, out_of_range losses via the VGG loss network; clip 2.0 + Adam), "
                                f"bs={B}/GPU {S}x{S} fp32",
                    "global_batch": B * world, "image_size": S,
                    "parallelism": f"data-parallel x{world}" + (" + SyncBatchNorm" if world > 1 else "")},
-        "roofline": {"bound": "mfma", "kernel": "loss-network conv3x3 fwd/dgrad launches of a step (split-bf16)",
-                     "achieved": tf, "peak": PEAK_SPLIT_BF16_TF, "unit": "TFLOP/s", "frac": tf / PEAK_SPLIT_BF16_TF,
-                     "fp32_mfma_peak": PEAK_FP32_MFMA_TF, "frac_of_fp32_mfma_peak": tf / PEAK_FP32_MFMA_TF,
-                     "traffic": None, "mfma_share_of_step": ms / args.steps / (elapsed / steps_timed * 1e3),
-                     "timing_source": "HIP events around each launch of 3 eager steps of the same shapes"},
-        "kernels_ms_per_step": {k: round(m / args.steps, 4) for k, (f, m, c) in sorted(fam.items())},
-        "mbgemm_tflops": (fam["mbgemm"][0] / (fam["mbgemm"][1] * 1e-3) / 1e12) if "mbgemm" in fam else None,
     }
+    if args.full:
+        # per-kernel-family times: HIP events around every launch of an eager step (a replayed graph
+        # launches nothing from Python), same kernels and shapes as the timed steps
+        eager = ASTTrainer(default_ast_args(batch_size=B * world), device=dev,
+                           ast=models.AST(attention=True).load_live_init(), graph=False)
+        ksteps = 3
+        eager.train_step(content, style, record=False)
+        torch.cuda.synchronize(dev)
+        timer = ops.LaunchTimer()
+        te = time.perf_counter()
+        with timer:
+            for _ in range(ksteps):
+                eager.train_step(content, style, record=False)
+        torch.cuda.synchronize(dev)
+        eager_ms = (time.perf_counter() - te) / ksteps * 1e3
+        del eager
+        fam = {}
+        for tag, fl, ms in timer.results():
+            k = tag.split()[0]
+            f0, m0, c0 = fam.get(k, (0.0, 0.0, 0))
+            fam[k] = (f0 + fl, m0 + ms, c0 + 1)
+        mm = [fam[k] for k in fam if k.startswith(("conv3x3", "wgrad"))]
+        fl, ms = sum(f for f, _, _ in mm), sum(m for _, m, _ in mm)
+        tf = fl / (ms * 1e-3) / 1e12 if ms else 0.0
+        result.update({   # the per-step kernel figures are per eager step
+            "eager_ms_per_step": eager_ms,
+            "roofline": {"bound": "mfma", "kernel": "loss-network conv3x3 fwd/dgrad launches of a step (split-bf16)",
+                         "achieved": tf, "peak": PEAK_SPLIT_BF16_TF, "unit": "TFLOP/s", "frac": tf / PEAK_SPLIT_BF16_TF,
+                         "fp32_mfma_peak": PEAK_FP32_MFMA_TF, "frac_of_fp32_mfma_peak": tf / PEAK_FP32_MFMA_TF,
+                         "traffic": None, "mfma_share_of_step": ms / ksteps / (elapsed / args.steps * 1e3),
+                         "timing_source": "HIP events around each launch of 3 eager steps of the same shapes"},
+            "kernels_ms_per_step": {k: round(m / ksteps, 4) for k, (f, m, c) in sorted(fam.items())},
+            "mbgemm_tflops": (fam["mbgemm"][0] / (fam["mbgemm"][1] * 1e-3) / 1e12) if "mbgemm" in fam else None,
+        })
     if rank == 0:
         print(json.dumps(result), flush=True)
 
@@ -330,6 +374,8 @@ def mobilenet_bench(args, dev, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out.float()).all(), "non-finite output"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"stylised": out}, rank, world)
     recs = timer.results()
     fam = {}
     attn = [0.0, 0.0, 0]
@@ -397,7 +443,7 @@ def mobilenet_bench(args, dev, rank, world):
                      "kernel_share_of_step": sum(m for _, _, m in recs) / args.steps / (step_s * 1e3)},
         "kernels": kernels,
     }
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         result["cpu_baseline"] = cpu_baseline_mobilenet(S, args.cpu_seconds, cpu_thread_options(args.cpu_threads),
                                                         args.attention)
     if rank == 0:
@@ -673,6 +719,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all(), "non-finite output"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"stylised": out}, rank, world)
 
     # ---- live roofline from the per-launch events ----
     recs = timer.results()
@@ -736,7 +784,7 @@ def main():
             a[1] += ms
         result["per_layer"] = {k: {"ms": v[1] / args.steps, "tflops": v[0] / (v[1] * 1e-3) / 1e12}
                                for k, v in sorted(layers.items())}
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         result["cpu_baseline"] = cpu_baseline(S, args.cpu_seconds, cpu_thread_options(args.cpu_threads))
     if rank == 0:
         print(json.dumps(result), flush=True)

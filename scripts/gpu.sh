@@ -6,8 +6,8 @@
 # gpurun_out/TAG_*. Tasks:
 #   tests            the -m gpu suite (no -x; per-test timeout)
 #   tests:EXPR       the -m gpu tests matching -k EXPR
-#   bench            bench.py default line (config 2, with its CPU baseline, as the driver runs it)
-#   bench:MODE       bench.py --mode MODE (no CPU baseline): train, mobilenet, ast-train, ae-train
+#   bench            bench.py --full (config 2 with its CPU baseline)
+#   bench:MODE       bench.py --full --mode MODE (no CPU baseline): train, mobilenet, ast-train, ae-train
 #   profiles         rocprofv3 kernel-trace stats + FETCH/WRITE_SIZE passes (scripts/measure_profiles.sh)
 #   clock            effective clock and MFMA busy of the config-2 conv dispatches (scripts/pmc_clock.sh)
 #   race             scripts/debug/race_probe4.py (16 repeats) and dp_repeat.py (8 runs) beside a
@@ -57,11 +57,11 @@ for task in "$@"; do
     tests) run_tests "" || exit 1 ;;
     tests:*) run_tests "${task#tests:}" "_k" || exit 1 ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/${TAG}_bench_fwd.json 2> $OUT/${TAG}_bench_fwd.err || exit 1
+      timeout -k 10 300 python bench.py --full > $OUT/${TAG}_bench_fwd.json 2> $OUT/${TAG}_bench_fwd.err || exit 1
       cut -c1-400 $OUT/${TAG}_bench_fwd.json ;;
     bench:*)
       m="${task#bench:}"
-      timeout -k 10 300 python bench.py --mode $m --cpu-seconds 0 > $OUT/${TAG}_bench_$m.json 2> $OUT/${TAG}_bench_$m.err || exit 1
+      timeout -k 10 300 python bench.py --full --mode $m --cpu-seconds 0 > $OUT/${TAG}_bench_$m.json 2> $OUT/${TAG}_bench_$m.err || exit 1
       cut -c1-400 $OUT/${TAG}_bench_$m.json ;;
     profiles) bash scripts/measure_profiles.sh ${TAG}m || exit 1 ;;
     clock) bash scripts/pmc_clock.sh ${TAG} fwd conv3x3 > $OUT/${TAG}_clock.txt 2>&1; rc=$?; cat $OUT/${TAG}_clock.txt; [ $rc -eq 0 ] || exit 1 ;;
