@@ -329,8 +329,10 @@ __global__ __launch_bounds__(WG4 ? 64 * ED4_WGN : 64, (K == 5 && KS >= 6) ? 1 : 
     }
   }
   psum += __shfl_xor(psum, 32, 64);
-  // one slot per (band, strip) of the image; strips past the right border (WG4 padding waves) store 0
-  if (h == 0 && chv) a.pool[((int64_t)n * a.hid + ch) * a.slots + band * (a.slots / bands) + s] = psum;
+  // one slot per (band, strip) of the image, the same layout in every form of the kernel (the ordered
+  // sum pairs slots by position, so a padded layout would round differently from the pool-only pass);
+  // strips past the right border (WG4 padding waves) have no slot
+  if (h == 0 && chv && s < strips) a.pool[((int64_t)n * a.hid + ch) * a.slots + band * strips + s] = psum;
 }
 
 
@@ -354,7 +356,7 @@ int launch_ks(EdArgs a, hipStream_t st) {
   // lose 10-50% to the per-row workgroup barrier (their rows are longer and less uniform)
   if (ED4_WG4 && K == 3 && a.wo % 8 == 0) {  // WG4: 4 strips per workgroup, 16-byte D stores
     const int64_t total4 = (int64_t)ncb * ((strips + ED4_WGN - 1) / ED4_WGN) * bands * a.n, grid4 = (total4 + 7) / 8 * 8;
-    if (ed_plan(a, (int64_t)bands * ((strips + ED4_WGN - 1) / ED4_WGN) * ED4_WGN)) return 0;
+    if (ed_plan(a, (int64_t)bands * strips)) return 0;
     hipLaunchKernelGGL((expand_dw4_kernel<K, KS, TH, PD, true, true, R1, UP>), dim3((unsigned)grid4), dim3(64 * ED4_WGN), 0, st, a,
                        strips, bands, ncb, (int)total4);
   } else if (ed_plan(a, (int64_t)bands * strips)) {
