@@ -130,6 +130,12 @@ SIGNATURES = {
     "ast_mbt_plane_act_f32": (_i, [_i, _p, _p, _p, _p, _p, _p, _ll, _ll, _p]),
     "ast_mbt_se_fc_fwd_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "ast_mbt_se_fc_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _p, _p, _p, _p, _p, _p, _ll, _p]),
+    "ast_color_convert_f32": (_i, [_p, _p, _i, _ll, _i, _p]),
+    "ast_color_convert_bf16_f32": (_i, [_p, _p, _i, _ll, _i, _p]),
+    "ast_color_convert_bf16": (_i, [_p, _p, _i, _ll, _i, _p]),
+    "ast_color_convert_backward_f32": (_i, [_p, _p, _p, _i, _ll, _i, _p]),
+    "ast_luma_transfer_f32": (_i, [_p, _p, _p, _i, _ll, _p]),
+    "ast_luma_transfer_bf16": (_i, [_p, _p, _p, _i, _ll, _p]),
 }
 
 ERRORS = {-1: "null pointer", -2: "bad shape", -3: "unsupported configuration"}

@@ -405,6 +405,28 @@ class AdaINFn(torch.autograd.Function):
         return dc, ds, None, None
 
 
+class ColorConvertFn(torch.autograd.Function):
+    """A colour conversion of model_util.py:11-140 (ops.color_convert, fp32 result) with the HIP
+    vector-Jacobian product as its backward; a bf16 input gets its gradient in bf16."""
+
+    @staticmethod
+    def forward(ctx, x, mode):
+        ctx.save_for_backward(x)
+        ctx.mode = mode
+        return ops.color_convert(x, mode)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.color_convert_backward(x.float(), g, ctx.mode).to(x.dtype), None
+
+
+def color_convert(x, mode):
+    if isinstance(x, torch.Tensor) and torch.is_grad_enabled() and x.requires_grad:
+        return ColorConvertFn.apply(x, mode)
+    return ops.color_convert(x, mode)
+
+
 def channel_stats(x, unbiased=True, eps=0.0):
     if torch.is_grad_enabled() and x.requires_grad:
         return ChannelStatsFn.apply(x, unbiased, eps)

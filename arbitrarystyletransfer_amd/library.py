@@ -28,6 +28,8 @@ mb_se_fold              mobilenetv2.py:63-81 folded into the pw conv --
 mb_pw                   mobilenetv2.py:162-165                       --
 mb_expand_gemm          models.py:335 (ada_out expand half)          --
 mb_conv3x3_dense        mobilenetv2.py:38-43, models.py:300-316      --
+color_convert           model_util.py:11-140 (six conversions)       d x
+luma_transfer           -- (colour-preserving recombination)         --
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -585,6 +587,60 @@ def _(x, wt, bias, act, out_bf16):
                        dtype=torch.bfloat16 if out_bf16 else torch.float32)
 
 
+# ------------------------------------------------------------------------------------------------
+# Colour spaces (model_util.py:11-140) and colour-preserving recombination
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::color_convert", mutates_args=())
+def color_convert(x: Tensor, mode: int, out_bf16: bool) -> Tensor:
+    """mode: an AST_COLOR_* code (ops.COLOR_MODES); fp32 result unless out_bf16 (bf16 input only)."""
+    return ops.color_convert(x, mode, torch.bfloat16 if out_bf16 else torch.float32)
+
+
+@register_fake("ast_hip::color_convert")
+def _(x, mode, out_bf16):
+    return x.new_empty(x.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+
+
+@custom_op("ast_hip::color_convert_backward", mutates_args=())
+def color_convert_backward(x: Tensor, grad: Tensor, mode: int) -> Tensor:
+    """J^T grad of color_convert at x (fp32). An op of its own, so that a traced backward
+    (torch.compile, AOT autograd) sees an opaque kernel with a fake implementation."""
+    return ops.color_convert_backward(x, grad, mode)
+
+
+@register_fake("ast_hip::color_convert_backward")
+def _(x, grad, mode):
+    return x.new_empty(x.shape)
+
+
+def _color_setup(ctx, inputs, output):
+    x, mode, out_bf16 = inputs
+    if out_bf16:
+        raise NotImplementedError("ast_hip::color_convert backward needs the float32 result (out_bf16=False)")
+    ctx.save_for_backward(x)
+    ctx.mode = mode
+
+
+def _color_backward(ctx, g):
+    (x,) = ctx.saved_tensors
+    return torch.ops.ast_hip.color_convert_backward(x.float(), g, ctx.mode).to(x.dtype), None, None
+
+
+register_autograd("ast_hip::color_convert", _color_backward, setup_context=_color_setup)
+
+
+@custom_op("ast_hip::luma_transfer", mutates_args=())
+def luma_transfer(stylised: Tensor, content: Tensor) -> Tensor:
+    """The Lab luminance of clamp01(stylised) with the a, b of clamp01(content), as RGB."""
+    return ops.luma_transfer(stylised, content)
+
+
+@register_fake("ast_hip::luma_transfer")
+def _(stylised, content):
+    return content.new_empty(content.shape)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
-                  "mb_conv3x3_dense"]
+                  "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer"]

@@ -19,7 +19,7 @@ from . import mbtrain, ops, synth
 from .conf import *  # noqa: F401,F403
 from .conf import device  # noqa: F401
 from .losses import *  # noqa: F401,F403
-from .model_util import channel_stats
+from .model_util import channel_stats, lab2rgb, rgb2lab  # noqa: F401  (re-exported, models.py:4)
 
 IMNET_MEAN = (0.485, 0.456, 0.406)   # models.py:189
 IMNET_STD = (0.229, 0.224, 0.225)    # models.py:190
@@ -102,6 +102,19 @@ def _compiling() -> bool:
 def _ops():
     from . import library  # noqa: F401  (registers the ast_hip::* custom ops)
     return torch.ops.ast_hip
+
+
+def _luma_transfer(stylised, content_img):
+    if _compiling():
+        return _ops().luma_transfer(stylised, content_img)
+    return ops.luma_transfer(stylised, content_img)
+
+
+def _color_convert(x, mode):
+    """ops.color_convert keeping x's dtype (fp32 -> fp32, bf16 -> bf16)."""
+    if _compiling():
+        return _ops().color_convert(x, ops.COLOR_MODES[mode], x.dtype == torch.bfloat16)
+    return ops.color_convert(x, mode, out_dtype=x.dtype)
 
 
 def _needs_grad(x, module):
@@ -362,7 +375,9 @@ class AdaINStyleTransfer(nn.Module):
     """encoder (VGG19 to relu4_1) -> AdaIN -> alpha blend -> mirrored decoder.
 
     forward(content_img, style_img, alpha=1.0) -> stylised image [B, 3, H, W]. Content and
-    style batches of the same shape are encoded in the same launches.
+    style batches of the same shape are encoded in the same launches. `preserve_color=True`
+    (inference only) keeps the content image's colours: the result is ops.luma_transfer(decoder
+    output, content_img), the stylised Lab luminance with the content's a and b.
     """
 
     def __init__(self, canonical: bool = False, enc_seed: int = 1, dec_seed: int = 2, weights="live"):
@@ -378,10 +393,20 @@ class AdaINStyleTransfer(nn.Module):
             return f[:b], f[b:]
         return self.encoder(content_img)[0], self.encoder(style_img)[0]
 
-    def forward(self, content_img, style_img, alpha: float = 1.0):
+    def _check_preserve_color(self, *imgs):
+        if torch.is_grad_enabled() and (any(i.requires_grad for i in imgs)
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("preserve_color is inference-only; run it under torch.no_grad()")
+
+    def forward(self, content_img, style_img, alpha: float = 1.0, preserve_color: bool = False):
+        if preserve_color:
+            self._check_preserve_color(content_img, style_img)
         f_c, f_s = self.encode_pair(content_img, style_img)
         t = self.adain(f_c, f_s, alpha=alpha)
-        return self.decoder(t)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
 
     # -- one style, many contents: the style owner encodes the style once and
     #    broadcasts its relu4_1 statistics (dp.broadcast_style_stats, 2*512 floats) --------------
@@ -391,13 +416,18 @@ class AdaINStyleTransfer(nn.Module):
         m, s = channel_stats(f_s)
         return m.flatten(1), s.flatten(1)
 
-    def stylize_with_stats(self, content_img, style_mean, style_std, alpha: float = 1.0):
-        """Stylise a content batch with given style statistics ([512] shared, or [N, 512])."""
+    def stylize_with_stats(self, content_img, style_mean, style_std, alpha: float = 1.0,
+                           preserve_color: bool = False):
+        """Stylise a content batch with given style statistics ([512] shared, or [N, 512]);
+        preserve_color as in forward."""
         if torch.is_grad_enabled() and (content_img.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_with_stats is inference-only; run it under torch.no_grad()")
         f_c = self.encoder(content_img)[0]
         t = ops.adain_stats(f_c, style_mean, style_std, alpha=alpha, swap_style_stats=not self.adain.canonical)
-        return self.decoder(t)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -547,14 +577,21 @@ class AST(nn.Module):
     (models.py:535-566). `attention=False` (default, the north-star path) stylises each layer with
     AdaIN(content_i, style_i); `attention=True` uses the reference's own choice, AdaAttN modules
     `ada_att_1` / `ada_att_2` (models.py:407-408, 557-558), each over enc_out_channels.
+    `lab_io=True` (with exporting=True only) is the reading of the commented models.py:427-429 and
+    529: both images go through rgb2lab on the way in and the result through lab2rgb on the way
+    out, in the tensors' own dtype (bf16 models: the bf16 -> bf16 colour kernels).
     Train mode with autograd (ASTTrainer, train.py:146-300) runs the training kernels: the
     detached eval-mode encoding of encode(detach=True), AdaAttN / ada_out / decoder with backward,
     and the train-mode (batch statistics) content encoding feeding org_out, as models.py:425-476.
     """
 
     def __init__(self, style_layers=[4, 7, 10, 12, 16], content_layers=[4, 7, 10, 12, 16], exporting=False,
-                 attention=False):
+                 attention=False, lab_io=False):
         super().__init__()
+        if lab_io and not exporting:
+            raise ValueError("lab_io=True needs exporting=True: the reference converts to Lab and back only "
+                             "on its exporting path (models.py:427-429, 529)")
+        self._lab_io = lab_io
         self._style_layers = style_layers
         self._content_layers = content_layers
         self._exporting = exporting
@@ -614,9 +651,15 @@ class AST(nn.Module):
         asserts 4-D maps (models.py:57), so this is the reading of the unparsable models.py:459
          under which the reference's training loop runs."""
         if self._exporting:
+            if self._lab_io:   # models.py:427-429: the network sees Lab images, in their own dtype
+                content_img = _color_convert(content_img, "rgb2lab")
+                style_img = _color_convert(style_img, "rgb2lab")
             t = self.encode(content_img, style_img)
             self._last_content_maps = None
-            return self._dec(t)
+            t_cs = self._dec(t)
+            if self._lab_io:   # models.py:529
+                t_cs = _color_convert(t_cs, "lab2rgb")
+            return t_cs
         st1, st2, t = self.encode(content_img, style_img, detach=True, return_maps=True)
         if self.training:
             # train mode: the content encoding for org_out uses batch statistics (and updates the

@@ -282,6 +282,87 @@ def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, s
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# Colour spaces (model_util.py:11-140) and colour-preserving recombination
+# ------------------------------------------------------------------------------------------------
+
+COLOR_MODES = {"rgb2xyz": 0, "xyz2rgb": 1, "xyz2lab": 2, "lab2xyz": 3, "rgb2lab": 4, "lab2rgb": 5}  # AST_COLOR_*
+
+
+def _color_mode(mode) -> int:
+    code = COLOR_MODES.get(mode, mode)
+    if isinstance(code, bool) or not isinstance(code, int) or not 0 <= code < len(COLOR_MODES):
+        raise HipOpError(f"colour mode must be one of {list(COLOR_MODES)}, got {mode!r}")
+    return code
+
+
+def _color_image(t: torch.Tensor, name: str) -> torch.Tensor:
+    dt = t.dtype if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 else torch.float32
+    t = _dev_typed(t, name, dt)
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise HipOpError(f"{name} must be [N, 3, H, W], got {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise HipOpError(f"{name} is empty: {tuple(t.shape)}")
+    return t
+
+
+def color_convert(x: torch.Tensor, mode, out_dtype: torch.dtype = torch.float32):
+    """One of the six conversions of model_util.py:11-140 (`mode`: a COLOR_MODES name or its code)
+    on an [N, 3, H, W] image, fp32 or bf16. The result is fp32 by default, as the reference
+    returns for either input; out_dtype=torch.bfloat16 (bf16 input only) keeps bf16 storage."""
+    code = _color_mode(mode)
+    x = _color_image(x, "x")
+    n, hw = int(x.shape[0]), int(x.shape[2] * x.shape[3])
+    L = lib()
+    if x.dtype == torch.float32 and out_dtype == torch.float32:
+        fn = L.ast_color_convert_f32
+    elif x.dtype == torch.bfloat16 and out_dtype == torch.float32:
+        fn = L.ast_color_convert_bf16_f32
+    elif x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16:
+        fn = L.ast_color_convert_bf16
+    else:
+        raise HipOpError(f"color_convert runs fp32->fp32, bf16->fp32 and bf16->bf16, not {x.dtype}->{out_dtype}")
+    out = torch.empty(x.shape, device=x.device, dtype=out_dtype)
+    nbytes = x.numel() * (x.element_size() + out.element_size())   # algorithmic: read x, write out
+    name = mode if isinstance(mode, str) else list(COLOR_MODES)[code]
+    check(_timed(f"color {name} {x.shape[2]}x{x.shape[3]}", -nbytes, x.device, lambda: fn(
+        ptr(x), ptr(out), n, hw, code, stream_ptr(x.device))), "color_convert")
+    return out
+
+
+def color_convert_backward(x: torch.Tensor, g: torch.Tensor, mode):
+    """J^T g of color_convert at x (fp32): the selected branch's derivative, zero where a clamp is
+    active; finite where the reference's autograd is NaN through its unselected branch."""
+    code = _color_mode(mode)
+    x, g = _dev(x, "x"), _dev(g, "grad")
+    if x.dim() != 4 or x.shape[1] != 3 or g.shape != x.shape or x.numel() == 0:
+        raise HipOpError(f"color_convert_backward needs equal [N, 3, H, W] x and grad: "
+                         f"{tuple(x.shape)} vs {tuple(g.shape)}")
+    n, hw = int(x.shape[0]), int(x.shape[2] * x.shape[3])
+    dx = torch.empty_like(x)
+    check(_timed(f"color bwd {code} {x.shape[2]}x{x.shape[3]}", -4 * 3 * x.numel(), x.device,
+                 lambda: lib().ast_color_convert_backward_f32(ptr(x), ptr(g), ptr(dx), n, hw, code,
+                                                              stream_ptr(x.device))), "color_convert_backward")
+    return dx
+
+
+def luma_transfer(stylised: torch.Tensor, content: torch.Tensor):
+    """Colour-preserving recombination in one launch: the Lab luminance of clamp01(stylised) with
+    the a, b of clamp01(content), back to RGB. Both [N, 3, H, W], both fp32 or both bf16."""
+    stylised = _color_image(stylised, "stylised")
+    content = _color_image(content, "content")
+    if stylised.shape != content.shape or stylised.dtype != content.dtype or stylised.device != content.device:
+        raise HipOpError(f"luma_transfer needs equal shapes and dtypes: {tuple(stylised.shape)} {stylised.dtype} vs "
+                         f"{tuple(content.shape)} {content.dtype}")
+    n, hw = int(content.shape[0]), int(content.shape[2] * content.shape[3])
+    out = torch.empty_like(content)
+    fn = lib().ast_luma_transfer_bf16 if content.dtype == torch.bfloat16 else lib().ast_luma_transfer_f32
+    nbytes = 3 * content.numel() * content.element_size()
+    check(_timed(f"luma_transfer {content.shape[2]}x{content.shape[3]}", -nbytes, content.device, lambda: fn(
+        ptr(stylised), ptr(content), ptr(out), n, hw, stream_ptr(content.device))), "luma_transfer")
+    return out
+
+
 def plane_normalize(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):
     x = _dev(x, "x")
     mean, std = _dev(mean, "mean"), _dev(std, "std")

@@ -654,6 +654,38 @@ int ast_mbt_se_fc_bwd_f32(const float* dgate, const float* z, const float* hid, 
                           float* dw1, float* db1, float* dw2, float* db2, float* dpool, float* workspace,
                           long long workspace_floats, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Colour spaces (model_util.py:11-140) on NCHW images with 3 channels: x, out [n][3][hw].
+ * mode: one AST_COLOR_* below. RGB2LAB and LAB2RGB include the reference's (lab/100 + 1)/2 and
+ * (x*2 - 1)*100 normalisation (model_util.py:117-140). The reference's constants and matrices
+ * (0.412453..., white point 0.95047, 1, 1.08883) and its NaN set: rgb below -0.055 and negative
+ * xyz components give NaN, lab2xyz / xyz2rgb clamp and stay finite. fp32 arithmetic throughout;
+ * _bf16_f32 reads bf16 and writes fp32 (what the reference returns), _bf16 writes bf16.
+ * backward: grad_in = J^T grad_out at x, the selected branch's derivative (zero where a clamp is
+ * active), finite where the reference's autograd is NaN through its unselected branch.
+ * AST_E_SHAPE for n <= 0, hw <= 0 or an unknown mode. */
+enum {
+  AST_COLOR_RGB2XYZ = 0,
+  AST_COLOR_XYZ2RGB = 1,
+  AST_COLOR_XYZ2LAB = 2,
+  AST_COLOR_LAB2XYZ = 3,
+  AST_COLOR_RGB2LAB = 4,
+  AST_COLOR_LAB2RGB = 5
+};
+int ast_color_convert_f32(const float* x, float* out, int n, long long hw, int mode, void* stream);
+int ast_color_convert_bf16_f32(const void* x, float* out, int n, long long hw, int mode, void* stream);
+int ast_color_convert_bf16(const void* x, void* out, int n, long long hw, int mode, void* stream);
+int ast_color_convert_backward_f32(const float* x, const float* grad_out, float* grad_in, int n,
+                                   long long hw, int mode, void* stream);
+
+/* Colour-preserving recombination, one launch: out = lab2rgb(cat(L of rgb2lab(clamp01(stylised)),
+ * ab of rgb2lab(clamp01(content)))), the stylised luminance with the content's chroma.
+ * stylised, content, out [n][3][hw], all fp32 or all bf16. */
+int ast_luma_transfer_f32(const float* stylised, const float* content, float* out, int n, long long hw,
+                          void* stream);
+int ast_luma_transfer_bf16(const void* stylised, const void* content, void* out, int n, long long hw,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
