@@ -94,22 +94,29 @@ std::tuple<at::Tensor, at::Tensor> channel_stats_meta(const at::Tensor& x, bool,
 }
 
 // ---- conv3x3: weight packing + the fused forward (PretrainedEncoder / VGG decoder convs) -----
-at::Tensor conv3x3_pack(const at::Tensor& w_) {
+// up2c: the extended pack -- the usual one with the collapsed slab of the upsampled reflect-pad conv appended
+at::Tensor conv3x3_pack(const at::Tensor& w_, bool up2c) {
   at::Tensor w = dev_f32(w_, "weight");
   TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3, "conv3x3 weight must be [cout, cin, 3, 3], got ",
               w.sizes());
   const int cout = (int)w.size(0), cin = (int)w.size(1);
   const c10::DeviceGuard guard(w.device());
-  at::Tensor out = at::empty({(int64_t)ast_conv3x3_packed_numel(cout, cin)}, w.options());
+  const int64_t base = (int64_t)ast_conv3x3_packed_numel(cout, cin);
+  at::Tensor out = at::empty({base + (up2c ? (int64_t)ast_conv3x3_up2c_numel(cout, cin) : 0)}, w.options());
   AST_CALL("conv3x3_pack", ast_conv3x3_pack_weights_f32(w.data_ptr<float>(), out.data_ptr<float>(), cout, cin,
                                                         cur_stream(w)));
+  if (up2c)
+    AST_CALL("conv3x3_pack up2c", ast_conv3x3_pack_up2c_f32(out.data_ptr<float>(), out.data_ptr<float>() + base, cout,
+                                                            cin, cur_stream(w)));
   return out;
 }
 
-at::Tensor conv3x3_pack_meta(const at::Tensor& w) {
+at::Tensor conv3x3_pack_meta(const at::Tensor& w, bool up2c) {
   TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3, "conv3x3 weight must be [cout, cin, 3, 3], got ",
               w.sizes());
-  return at::empty({(int64_t)ast_conv3x3_packed_numel((int)w.size(0), (int)w.size(1))}, w.options());
+  const int cout = (int)w.size(0), cin = (int)w.size(1);
+  return at::empty({(int64_t)ast_conv3x3_packed_numel(cout, cin) +
+                    (up2c ? (int64_t)ast_conv3x3_up2c_numel(cout, cin) : 0)}, w.options());
 }
 
 struct ConvShape {
@@ -124,7 +131,9 @@ ConvShape conv_shape(const at::Tensor& x, const at::Tensor& w_packed, int64_t co
   TORCH_CHECK(want_pre || want_act || want_pool, "conv3x3: no output requested");
   TORCH_CHECK(cout > 0, "cout must be positive");
   ConvShape s{x.size(0), x.size(1), x.size(2), x.size(3), x.size(2) * upsample, x.size(3) * upsample};
-  TORCH_CHECK(w_packed.numel() == (int64_t)ast_conv3x3_packed_numel((int)cout, (int)s.cin),
+  const int64_t base = (int64_t)ast_conv3x3_packed_numel((int)cout, (int)s.cin);
+  TORCH_CHECK(w_packed.numel() == base ||  // or the extended pack (conv3x3_pack(w, up2c=True))
+                  w_packed.numel() == base + (int64_t)ast_conv3x3_up2c_numel((int)cout, (int)s.cin),
               "packed weight does not match (cout, cin)");
   TORCH_CHECK(!want_pool || (s.H >= 2 && s.W >= 2), "max-pool needs H, W >= 2");
   return s;
@@ -156,6 +165,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> conv3x3_fwd(
     return want ? at::empty({s.n, cout, h, w}, x.options()) : at::empty({0}, x.options());
   };
   at::Tensor pre = mk(want_pre, s.H, s.W), act = mk(want_act, s.H, s.W), pool = mk(want_pool, s.H / 2, s.W / 2);
+  const int64_t base = (int64_t)ast_conv3x3_packed_numel((int)cout, (int)s.cin);
+  if (w_packed.numel() > base && upsample == 2 && pad_mode == 1 && !want_pool && s.cin >= 16 && !in_mean && cfg < 0) {
+    // the collapsed slab of an extended pack: 2x2 taps per output phase (as ops.conv3x3)
+    AST_CALL("conv3x3 up2c", ast_conv3x3_up2c_fwd_f32(
+                                 x.data_ptr<float>(), nullptr, 0, w_packed.data_ptr<float>() + base, fptr(bias),
+                                 want_pre ? pre.data_ptr<float>() : nullptr, want_act ? act.data_ptr<float>() : nullptr,
+                                 (int)s.n, (int)s.cin, (int)s.h_in, (int)s.w_in, (int)cout, (int)upsample,
+                                 (int)pad_mode, cur_stream(x)));
+    return {pre, act, pool};
+  }
   AST_CALL("conv3x3", ast_conv3x3_fwd_f32_cfg(
                           (int)cfg, x.data_ptr<float>(), nullptr, 0, w_packed.data_ptr<float>(), fptr(bias),
                           want_pre ? pre.data_ptr<float>() : nullptr, want_act ? act.data_ptr<float>() : nullptr,
@@ -200,7 +219,7 @@ at::Tensor gram_meta(const at::Tensor& f) {
 TORCH_LIBRARY(ast_hip, m) {
   m.def("adain(Tensor content_map, Tensor style_map, float alpha=1.0, bool swap_style_stats=True) -> Tensor");
   m.def("channel_stats(Tensor x, bool unbiased=True, float eps=0.0) -> (Tensor, Tensor)");
-  m.def("conv3x3_pack(Tensor weight) -> Tensor");
+  m.def("conv3x3_pack(Tensor weight, bool up2c=False) -> Tensor");
   m.def("conv3x3_fwd(Tensor x, Tensor w_packed, Tensor? bias, int cout, int upsample=1, int pad_mode=0, "
         "Tensor? in_mean=None, Tensor? in_std=None, bool want_pre=False, bool want_act=True, bool want_pool=False, "
         "int cfg=-1) -> (Tensor, Tensor, Tensor)");

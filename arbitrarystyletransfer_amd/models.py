@@ -152,14 +152,15 @@ class _PackedConvCache:
     def __init__(self):
         self._cache = {}
 
-    def get(self, conv: nn.Conv2d) -> torch.Tensor:
+    def get(self, conv: nn.Conv2d, up2c: bool = False) -> torch.Tensor:
+        """up2c: the extended pack (ops.pack_conv3x3), built when and as often as the plain one."""
         w = conv.weight
-        key = id(conv)
+        key = (id(conv), up2c)
         stamp = (w.data_ptr(), w._version, w.device, ops.weight_epoch(w))
         hit = self._cache.get(key)
         if hit is not None and hit[0] == stamp:
             return hit[1]
-        packed = ops.pack_conv3x3(w.detach())
+        packed = ops.pack_conv3x3(w.detach(), up2c=up2c)
         self._cache[key] = (stamp, packed)
         return packed
 
@@ -337,6 +338,8 @@ class VGGDecoder(nn.Sequential):
         if weights == "live":
             self.load_live_init(seed)
         object.__setattr__(self, "_packed", _PackedConvCache())
+        # the upsampled convs take the extended pack: the collapsed 2x2-taps-per-phase kernel (AST_CONV_UP2C=0: 9 taps)
+        object.__setattr__(self, "_up2c", ops.up2c_enabled())
 
     def convs(self):
         return [g[0] for g in self._groups]
@@ -348,11 +351,16 @@ class VGGDecoder(nn.Sequential):
             conv.bias.copy_(torch.from_numpy(b))
 
     def forward(self, x):
+        # inference (eager and compiled: the same bits) takes the extended pack on the upsampled convs.
+        # Under autograd the module keeps plain packs: its forward stays bit-equal to DecoderConvFn
+        # layers applied with ops.pack_conv3x3(w) (tests/test_gpu_dgrad_fused.py); DecoderConvFn and
+        # the ast_hip::conv3x3 op themselves accept either pack
         if _compiling():
             A = _ops()
+            tail = self._up2c and not _needs_grad(x, self)
             for conv, up, relu in self._groups:
-                pre, act, _ = A.conv3x3(x, conv.weight, A.conv3x3_pack(conv.weight.detach()), conv.bias,
-                                        2 if up else 1, 1, None, None, not relu, relu, False, None)
+                pre, act, _ = A.conv3x3(x, conv.weight, A.conv3x3_pack(conv.weight.detach(), up and tail),
+                                        conv.bias, 2 if up else 1, 1, None, None, not relu, relu, False, None)
                 x = act if relu else pre
             return x
         if _needs_grad(x, self):
@@ -364,7 +372,7 @@ class VGGDecoder(nn.Sequential):
                                            k > 0 and g[k - 1][2], relu and k + 1 < len(g))
             return x
         for conv, up, relu in self._groups:
-            pre, act, _ = ops.conv3x3(x, self._packed.get(conv), conv.bias, conv.out_channels,
+            pre, act, _ = ops.conv3x3(x, self._packed.get(conv, up and self._up2c), conv.bias, conv.out_channels,
                                       upsample=2 if up else 1, pad_mode="reflect",
                                       want_pre=not relu, want_act=relu)
             x = act if relu else pre

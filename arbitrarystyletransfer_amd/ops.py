@@ -103,15 +103,35 @@ def tuned_config(n, cin, h_in, w_in, cout, up, pad_mode, pool, kind="") -> int:
     k = f"{n}x{cin}x{h_in}x{w_in}->{cout} up{up} {pad_mode}{' pool' if pool else ''}{kind}"
     return int(_TUNING.get(k, -1))
 
-def pack_conv3x3(weight: torch.Tensor) -> torch.Tensor:
-    """Repack a [cout, cin, 3, 3] filter bank into the kernel's [cin_pad][9][cout_pad] layout."""
+
+_UP2C = None
+
+
+def up2c_enabled() -> bool:
+    """AST_CONV_UP2C=0: the model packs its upsampled decoder convs without the collapsed slab, so
+    they run the 9-tap kernel (A/B runs). Read once per process."""
+    global _UP2C
+    if _UP2C is None:
+        _UP2C = os.environ.get("AST_CONV_UP2C", "1") != "0"
+    return _UP2C
+
+
+def pack_conv3x3(weight: torch.Tensor, up2c: bool = False) -> torch.Tensor:
+    """Repack a [cout, cin, 3, 3] filter bank into the kernel's [cin_pad][9][cout_pad] layout.
+    up2c: the extended pack -- the usual one with the collapsed slab of the upsampled reflect-pad
+    conv (2x2 taps per output phase, csrc/conv3x3_igemm.hip) appended; conv3x3 accepts either."""
     w = _dev(weight, "weight")
     if w.dim() != 4 or w.shape[2:] != (3, 3):
         raise HipOpError(f"conv3x3 weight must be [cout, cin, 3, 3], got {tuple(w.shape)}")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     L = lib()
-    out = torch.empty(int(L.ast_conv3x3_packed_numel(cout, cin)), device=w.device, dtype=torch.float32)
+    base = int(L.ast_conv3x3_packed_numel(cout, cin))
+    tail = int(L.ast_conv3x3_up2c_numel(cout, cin)) if up2c else 0
+    out = torch.empty(base + tail, device=w.device, dtype=torch.float32)
     check(L.ast_conv3x3_pack_weights_f32(ptr(w), ptr(out), cout, cin, stream_ptr(w.device)), "pack_conv3x3")
+    if up2c:
+        check(L.ast_conv3x3_pack_up2c_f32(ptr(out), ptr(out[base:]), cout, cin, stream_ptr(w.device)),
+              "pack_conv3x3 up2c")
     return out
 
 
@@ -152,7 +172,9 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, *, upsampl
             raise HipOpError(f"x2 {tuple(x2.shape)} must match x {tuple(x.shape)} in C, H, W")
         n2 = int(x2.shape[0])
     n = n1 + n2
-    if w_packed.numel() != int(lib().ast_conv3x3_packed_numel(cout, cin)):
+    base = int(lib().ast_conv3x3_packed_numel(cout, cin))
+    has_tail = w_packed.numel() == base + int(lib().ast_conv3x3_up2c_numel(cout, cin))   # extended pack
+    if w_packed.numel() != base and not has_tail:
         raise HipOpError("packed weight does not match (cout, cin)")
     if bias is not None:
         bias = _dev(bias, "bias")
@@ -175,6 +197,9 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, *, upsampl
         raise HipOpError("max-pool needs H, W >= 2")
     if pre is None and act is None and pool is None:
         raise HipOpError("conv3x3: no output requested")
+    # the collapsed slab of an extended pack: 2x2 taps per output phase (4 products per output, not 9)
+    up2c = (has_tail and upsample == 2 and pad_mode == "reflect" and not want_pool and cin >= 16
+            and in_mean is None and cfg < 0)
     if cfg < 0:
         cfg = tuned_config(n, cin, h_in, w_in, cout, upsample, pad_mode, want_pool)
     G, gap = pack_plan(n, w_in, want_pool) if (_pack and pad_mode == "zeros" and upsample == 1
@@ -195,8 +220,14 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, *, upsampl
                       "unpack")
             res.append(full if t is not None else None)
         return tuple(res)
-    flops = _flops if _flops is not None else 2 * n * H * W * cout * cin * 9
+    flops = _flops if _flops is not None else 2 * n * H * W * cout * cin * 9   # algorithmic (9 taps)
     tag = f"conv3x3 {cin}->{cout} {H}x{W} up{upsample} {pad_mode}"
+    if up2c:
+        code = _timed(tag, flops, x.device, lambda: lib().ast_conv3x3_up2c_fwd_f32(
+            ptr(x), ptr(x2), n2, ptr(w_packed[base:]), ptr(bias), ptr(pre), ptr(act), n1, cin, h_in, w_in, cout,
+            upsample, PAD_MODES[pad_mode], stream_ptr(x.device)))
+        check(code, "conv3x3 up2c")
+        return pre, act, pool
     code = _timed(tag, flops, x.device, lambda: lib().ast_conv3x3_fwd_f32_cfg(
         cfg, ptr(x), ptr(x2), n2, ptr(w_packed), ptr(bias), ptr(pre), ptr(act), ptr(pool), ptr(in_mean),
         ptr(in_std), n1, cin, h_in, w_in, cout, upsample, PAD_MODES[pad_mode], stream_ptr(x.device)))

@@ -88,6 +88,22 @@ int ast_conv3x3_fwd_f32_cfg(int cfg, const float* x, const float* x2, int n2,
                             int n, int cin, int h_in, int w_in, int cout,
                             int upsample, int pad_mode, void* stream);
 
+/* Collapsed form of the upsampled decoder convs (nearest x2 -> ReflectionPad2d(1) -> conv3x3): the 9
+ * taps of an output pixel touch 4 source pixels, so each output phase (row & 1, col & 1) is a 2x2
+ * conv of the source with tap sums of w: 16 phase-taps per source pixel instead of 36 tap
+ * applications. The collapsed slab (split-bf16, ast_conv3x3_up2c_numel floats, 16-byte aligned) is
+ * derived from the fp32 part of a packed buffer, once per parameter version. The forward covers
+ * upsample = 2, pad_mode = 1 (reflect), cin >= 16, outputs y_pre and / or y_act; anything else
+ * returns AST_E_UNSUPPORTED (run ast_conv3x3_fwd_f32_cfg instead). Results differ from the 9-tap
+ * kernels' by the fp32 rounding of the tap sums; an output reached by a non-finite input is
+ * non-finite in both, but may be +-inf here where the 9-tap form gives NaN (opposite-sign taps). */
+size_t ast_conv3x3_up2c_numel(int cout, int cin);
+int ast_conv3x3_pack_up2c_f32(const float* w_packed, float* w_up2c, int cout, int cin, void* stream);
+int ast_conv3x3_up2c_fwd_f32(const float* x, const float* x2, int n2, const float* w_up2c,
+                             const float* bias, float* y_pre, float* y_act,
+                             int n, int cin, int h_in, int w_in, int cout,
+                             int upsample, int pad_mode, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-channel statistics and AdaIN.
  * ------------------------------------------------------------------------------------------ */
