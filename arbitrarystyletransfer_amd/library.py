@@ -30,6 +30,9 @@ mb_expand_gemm          models.py:335 (ada_out expand half)          --
 mb_conv3x3_dense        mobilenetv2.py:38-43, models.py:300-316      --
 color_convert           model_util.py:11-140 (six conversions)       d x
 luma_transfer           -- (colour-preserving recombination)         --
+resize_labels           -- (nearest resize of uint8 label maps)      --
+region_stats            -- (masked per-region channel statistics)    --
+adain_regions           -- (regional multi-style AdaIN)              --
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -641,6 +644,48 @@ def _(stylised, content):
     return content.new_empty(content.shape)
 
 
+# ------------------------------------------------------------------------------------------------
+# Regional multi-style AdaIN (csrc/adain_regions.hip; inference only, no autograd)
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::resize_labels", mutates_args=())
+def resize_labels(labels: Tensor, h: int, w: int) -> Tensor:
+    """Nearest-neighbour resize of uint8 label maps [N, H, W] to [N, h, w]."""
+    return ops.resize_labels(labels, h, w)
+
+
+@register_fake("ast_hip::resize_labels")
+def _(labels, h, w):
+    return labels.new_empty((labels.shape[0], h, w))
+
+
+@custom_op("ast_hip::region_stats", mutates_args=())
+def region_stats(x: Tensor, labels: Tensor, regions: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per-region mean and unbiased std [N, regions, C] and pixel counts [N, regions] (int32)."""
+    return ops.region_stats(x, labels, regions)
+
+
+@register_fake("ast_hip::region_stats")
+def _(x, labels, regions):
+    n, c = x.shape[:2]
+    return (x.new_empty((n, regions, c)), x.new_empty((n, regions, c)),
+            x.new_empty((n, regions), dtype=torch.int32))
+
+
+@custom_op("ast_hip::adain_regions", mutates_args=())
+def adain_regions(content: Tensor, labels: Tensor, style_mean: Tensor, style_std: Tensor, mix: Tensor, alpha: float,
+                  swap_style_stats: bool) -> Tensor:
+    """Per-region AdaIN against a per-region mix of the rows of a style-statistics table."""
+    return ops.adain_regions(content, labels, style_mean, style_std, mix, alpha=alpha,
+                             swap_style_stats=swap_style_stats)
+
+
+@register_fake("ast_hip::adain_regions")
+def _(content, labels, style_mean, style_std, mix, alpha, swap_style_stats):
+    return torch.empty_like(content)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
-                  "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer"]
+                  "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
+                  "region_stats", "adain_regions"]

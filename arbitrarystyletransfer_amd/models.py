@@ -437,6 +437,105 @@ class AdaINStyleTransfer(nn.Module):
             return _luma_transfer(out, content_img)
         return out
 
+    # -- several styles: interpolation and / or one mix of styles per region of the content --------
+    def stylize_regions(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
+                        style_labels=None, preserve_color: bool = False):
+        """Stylise content_img [N, 3, H, W] with the S styles style_imgs [S, 3, Hs, Ws] (shared by
+        the batch), region by region (ops.adain_regions on the relu4_1 maps; inference only).
+
+        labels: uint8 [N, H, W] or [H, W], at image or already at relu4_1 resolution; region k is
+        the pixels labelled k, a label >= K (255 by convention) leaves the pixel's features alone.
+        None: one region, i.e. plain style interpolation.
+        weights: host-side [K, S] or [N, K, S] (nested sequence or CPU tensor), non-negative, each
+        row normalised to sum 1: region k moves to the weights[k]-mix of the styles' statistics.
+        None: region k takes style k (K = S), or equal weights when labels is None.
+        style_labels: uint8 [S, Hs, Ws] with the same region ids: region k then takes the
+        statistics of each style's own region k instead of the whole style map (K * S <= 64).
+        preserve_color as in forward."""
+        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("stylize_regions is inference-only; run it under torch.no_grad()")
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError("stylize_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
+        w = region_weights(weights, n, s, single_region=labels is None)
+        k = int(w.shape[1])
+        if s * (k if style_labels is not None else 1) > ops.MAX_STYLE_ROWS:
+            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} rows of style statistics (S, or K * S with style_labels)")
+        f_c = self.encoder(content_img)[0]
+        f_s = self.encoder(style_imgs)[0]
+        if labels is None:
+            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
+        else:
+            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels")
+        if style_labels is None:
+            mean, std = channel_stats(f_s)
+            mean, std = mean.flatten(1), std.flatten(1)                       # [S, C]
+            mix = w
+        else:
+            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels")
+            rm, rs, _ = ops.region_stats(f_s, sl, k)                          # [S, K, C]
+            c = int(f_s.shape[1])
+            mean = rm.transpose(0, 1).reshape(k * s, c)                       # row k * S + s
+            std = rs.transpose(0, 1).reshape(k * s, c)
+            mix = torch.zeros((w.shape[0], k, k * s), dtype=torch.float64)    # block-wise: region k reads block k
+            for r in range(k):
+                mix[:, r, r * s:(r + 1) * s] = w[:, r]
+        t = ops.adain_regions(f_c, lab, mean, std, mix.float().to(f_c.device), alpha=alpha,
+                              swap_style_stats=not self.adain.canonical)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
+
+
+def region_weights(weights, n: int, s: int, single_region: bool = False):
+    """The [1 or N, K, S] float64 CPU mix of stylize_regions from its `weights` argument (None, a
+    nested sequence or a CPU tensor of shape [K, S] or [N, K, S]): entries non-negative and finite,
+    every row summing to more than 0 (else ValueError), rows normalised to sum 1 in float64."""
+    if weights is None:
+        if single_region:
+            return torch.full((1, 1, s), 1.0 / s, dtype=torch.float64)
+        if s > ops.MAX_REGIONS:
+            raise ValueError(f"weights=None assigns style k to region k: at most {ops.MAX_REGIONS} styles, got {s}")
+        return torch.eye(s, dtype=torch.float64).unsqueeze(0)
+    if isinstance(weights, torch.Tensor) and weights.device.type != "cpu":
+        raise ValueError("weights are host-side: pass a nested sequence or a CPU tensor")
+    try:
+        w = torch.as_tensor(weights, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"weights must be a [K, S] or [N, K, S] array of numbers: {e}") from None
+    if w.dim() == 2:
+        w = w.unsqueeze(0)
+    if w.dim() != 3 or w.shape[2] != s or w.shape[0] not in (1, n) or not 1 <= w.shape[1] <= ops.MAX_REGIONS:
+        raise ValueError(f"weights must be [K, S] or [N, K, S] with N={n}, S={s}, K in 1..{ops.MAX_REGIONS}; "
+                         f"got {tuple(w.shape)}")
+    if single_region and w.shape[1] != 1:
+        raise ValueError(f"labels=None is a single region: weights must have K = 1, got K = {w.shape[1]}")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("weights must be finite and non-negative")
+    tot = w.sum(dim=2, keepdim=True)
+    if bool((tot <= 0).any()):
+        raise ValueError("every row of weights must sum to more than 0")
+    return w / tot
+
+
+def _feature_labels(labels, n, img_hw, feat_hw, name):
+    """uint8 labels [n, H, W] or [H, W], at image or feature resolution -> [n, h, w] at feature
+    resolution (ops.resize_labels when needed)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() not in (2, 3):
+        raise ValueError(f"{name} must be a uint8 tensor [N, H, W] or [H, W]")
+    if labels.dim() == 2:
+        labels = labels.unsqueeze(0).expand(n, -1, -1)
+    if labels.shape[0] != n:
+        raise ValueError(f"{name} has {labels.shape[0]} maps for a batch of {n}")
+    hw, img_hw, feat_hw = tuple(labels.shape[1:]), tuple(img_hw), tuple(feat_hw)
+    if hw != feat_hw and hw != img_hw:
+        raise ValueError(f"{name} must be at the image resolution {img_hw} or the feature resolution {feat_hw}, "
+                         f"got {hw}")
+    labels = labels.contiguous()
+    return labels if hw == feat_hw else ops.resize_labels(labels, feat_hw[0], feat_hw[1])
+
 
 # ------------------------------------------------------------------------------------------------
 # MobileNet-style variant (SURVEY.md §3.2, §8a A7-A9): Encoder -> per-layer AdaIN -> ada_out ->

@@ -297,6 +297,97 @@ def _dev_typed(t: torch.Tensor, name: str, dtype: torch.dtype) -> torch.Tensor:
     return t.contiguous()
 
 
+# Regional multi-style AdaIN (csrc/adain_regions.hip): AST_MAX_REGIONS / AST_MAX_STYLE_ROWS of ast_hip.h
+MAX_REGIONS = 8
+MAX_STYLE_ROWS = 64
+
+
+def _labels(t: torch.Tensor, name: str) -> torch.Tensor:
+    if isinstance(t, torch.Tensor) and t.dtype != torch.uint8:
+        raise HipOpError(f"{name} must be uint8, got {t.dtype}")
+    t = _dev_typed(t, name, torch.uint8)
+    if t.dim() != 3 or t.numel() == 0:
+        raise HipOpError(f"{name} must be a non-empty [N, H, W] uint8 map, got {tuple(t.shape)}")
+    return t
+
+
+def _regions(regions) -> int:
+    if isinstance(regions, bool) or not isinstance(regions, int) or not 1 <= regions <= MAX_REGIONS:
+        raise HipOpError(f"regions must be an int in 1..{MAX_REGIONS}, got {regions!r}")
+    return regions
+
+
+def resize_labels(labels: torch.Tensor, h: int, w: int):
+    """Nearest-neighbour resize of uint8 label maps [N, H, W] to [N, h, w]: src = (dst * in) // out
+    per axis, the pixel F.interpolate(mode="nearest") picks."""
+    labels = _labels(labels, "labels")
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0:
+        raise HipOpError(f"resize_labels needs a positive size, got {(h, w)}")
+    n, hs, ws = (int(s) for s in labels.shape)
+    out = torch.empty((n, h, w), device=labels.device, dtype=torch.uint8)
+    check(lib().ast_resize_labels_u8(ptr(labels), ptr(out), n, hs, ws, h, w, stream_ptr(labels.device)),
+          "resize_labels")
+    return out
+
+
+def _map_and_labels(x, labels, what):
+    if isinstance(labels, torch.Tensor) and labels.dtype != torch.uint8:
+        raise HipOpError(f"labels must be uint8, got {labels.dtype}")
+    x = _dev(x, what)
+    labels = _labels(labels, "labels")
+    if x.dim() != 4 or x.numel() == 0:
+        raise HipOpError(f"{what} must be a non-empty NCHW map, got {tuple(x.shape)}")
+    n, c, h, w = (int(s) for s in x.shape)
+    if tuple(labels.shape) != (n, h, w) or labels.device != x.device:
+        raise HipOpError(f"labels must be [N, H, W] = {(n, h, w)} on {x.device}, got {tuple(labels.shape)} "
+                         f"on {labels.device}")
+    return x, labels, n, c, h, w
+
+
+def region_stats(x: torch.Tensor, labels: torch.Tensor, regions: int):
+    """Per-region channel statistics of x [N, C, H, W] under labels [N, H, W] (uint8; a label
+    >= regions belongs to no region): mean and unbiased std [N, regions, C] and pixel counts
+    [N, regions] (int32). An empty region has NaN mean and std, a one-pixel region NaN std."""
+    regions = _regions(regions)
+    x, labels, n, c, h, w = _map_and_labels(x, labels, "x")
+    mean = torch.empty((n, regions, c), device=x.device, dtype=torch.float32)
+    std = torch.empty_like(mean)
+    count = torch.empty((n, regions), device=x.device, dtype=torch.int32)
+    check(lib().ast_region_stats_f32(ptr(x), ptr(labels), ptr(mean), ptr(std), ptr(count), n, c, h, w, regions,
+                                     stream_ptr(x.device)), "region_stats")
+    return mean, std, count
+
+
+def adain_regions(content: torch.Tensor, labels: torch.Tensor, style_mean: torch.Tensor, style_std: torch.Tensor,
+                  mix: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
+    """Regional multi-style AdaIN in one launch. Region k of sample n (the pixels with
+    labels[n] == k) is normalised with its own statistics and moved to the mix
+    sum_t mix[n, k, t] * (style_mean, style_std)[t] of the rows of a style-statistics table [T, C];
+    pixels labelled >= K pass through bit for bit. mix is [K, T] or [1, K, T] (shared by the batch)
+    or [N, K, T]; rows with weight exactly 0 are skipped. alpha and swap_style_stats as adain_stats."""
+    content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
+    m, s, mix = _dev(style_mean, "style_mean"), _dev(style_std, "style_std"), _dev(mix, "mix")
+    if m.dim() != 2 or m.shape != s.shape or m.shape[1] != c or not 1 <= m.shape[0] <= MAX_STYLE_ROWS:
+        raise HipOpError(f"style statistics must be two [T, C={c}] tables with T in 1..{MAX_STYLE_ROWS}, got "
+                         f"{tuple(m.shape)} and {tuple(s.shape)}")
+    rows = int(m.shape[0])
+    if mix.dim() == 2:
+        mix = mix.unsqueeze(0)
+    if mix.dim() != 3 or mix.shape[0] not in (1, n) or not 1 <= mix.shape[1] <= MAX_REGIONS or mix.shape[2] != rows:
+        raise HipOpError(f"mix must be [N={n} or 1, K <= {MAX_REGIONS}, T={rows}], got {tuple(mix.shape)}")
+    regions = int(mix.shape[1])
+    shared = mix.shape[0] == 1   # one sample: either stride reads the same row
+    out = torch.empty_like(content)
+    nbytes = 4 * 2 * content.numel() + labels.numel()   # algorithmic: read c and the label map, write out
+    check(_timed(f"adain_regions {c}ch {h}x{w} K{regions}", -nbytes, content.device,
+                 lambda: lib().ast_adain_regions_f32(
+                     ptr(content), ptr(labels), ptr(m), ptr(s), ptr(mix), ptr(out), n, c, h, w, regions, rows,
+                     0 if shared else regions * rows, float(alpha), 1 if swap_style_stats else 0,
+                     stream_ptr(content.device))), "adain_regions")
+    return out
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

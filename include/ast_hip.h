@@ -138,6 +138,35 @@ int ast_adain_backward_f32(const float* content, const float* style, const float
                            float* d_content, float* d_style, int n, int c, int hc, int wc,
                            int hs, int ws, double alpha, int swap_style_stats, void* stream);
 
+/* Regional multi-style AdaIN (csrc/adain_regions.hip; an extension, no reference counterpart).
+ * labels [n, h, w] uint8, shared by the c planes of a sample: label k < regions puts the pixel in
+ * region k, any label >= regions (255 by convention) passes it through untouched and keeps it out
+ * of every statistic. Region statistics are the two-pass mean and unbiased std (no eps) over the
+ * region's pixels only: NaN mean and std for an empty region, NaN std for a one-pixel region. */
+#define AST_MAX_REGIONS 8
+#define AST_MAX_STYLE_ROWS 64
+
+/* Nearest-neighbour resize of label maps [n, hs, ws] -> [n, hd, wd]: src = (dst * in) / out per
+ * axis in integer arithmetic (what F.interpolate(mode="nearest") picks). */
+int ast_resize_labels_u8(const unsigned char* src, unsigned char* dst, long long n,
+                         int hs, int ws, int hd, int wd, void* stream);
+
+/* mean, std [n, regions, c] and count [n, regions] (int32) of x [n, c, h, w] per region. */
+int ast_region_stats_f32(const float* x, const unsigned char* labels, float* mean, float* std,
+                         int* count, int n, int c, int h, int w, int regions, void* stream);
+
+/* One launch: for region k of sample n and channel ch, (m, s) = sum_t mix[n, k, t] * (style_mean,
+ * style_std)[t, ch] over the `rows` rows of the table [rows, c] (rows with weight exactly 0 are
+ * skipped, so they may hold NaN), (scale, shift) = (m, s) when swap_style_stats, else (s, m), and
+ *   out = alpha * ((c - mu_k) / sd_k * scale + shift) + (1 - alpha) * c      on the region's pixels,
+ *   out = c bit for bit                                                     where label >= regions.
+ * mix [n or 1, regions, rows]; regions 1..AST_MAX_REGIONS, rows 1..AST_MAX_STYLE_ROWS. */
+int ast_adain_regions_f32(const float* content, const unsigned char* labels,
+                          const float* style_mean, const float* style_std, const float* mix,
+                          float* out, int n, int c, int h, int w, int regions, int rows,
+                          int mix_stride_n /* 0: one mix for the batch, else regions*rows */,
+                          double alpha, int swap_style_stats, void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
