@@ -41,6 +41,12 @@ SIGNATURES = {
     "ast_resize_labels_u8": (_i, [_p, _p, _ll, _i, _i, _i, _i, _p]),
     "ast_region_stats_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ast_adain_regions_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p]),
+    "ast_efdm_workspace_bytes": (_ll, [_i, _i, _i, _ll, _ll]),
+    "ast_efdm_ex_workspace_bytes": (_ll, [_i, _i, _i, _ll, _ll, _i]),
+    "ast_efdm_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
+    "ast_efdm_ex_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _ll, _p]),
+    "ast_plane_sort_workspace_bytes": (_ll, [_ll, _ll, _i, _i]),
+    "ast_plane_sort_f32": (_i, [_p, _p, _p, _ll, _ll, _i, _p, _ll, _p]),
     "ast_conv3x3_pack_weights_ex_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ast_conv_act_backward_f32": (_i, [_p, _p, _p, _p, _p, _ll, _i, _i, _p]),
     "ast_relu_mask_f32": (_i, [_p, _p, _p, _ll, _p]),

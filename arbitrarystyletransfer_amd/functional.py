@@ -405,6 +405,20 @@ class AdaINFn(torch.autograd.Function):
         return dc, ds, None, None
 
 
+class EFDMFn(torch.autograd.Function):
+    """Exact feature distribution matching (ops.efdm) with the paper's straight-through gradient,
+    `content + (matched - content).detach()`: grad_content = grad_out (with the alpha blend too),
+    none for the style. The backward launches nothing."""
+
+    @staticmethod
+    def forward(ctx, content, style, alpha):
+        return ops.efdm(content, style, alpha=alpha)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None
+
+
 class ColorConvertFn(torch.autograd.Function):
     """A colour conversion of model_util.py:11-140 (ops.color_convert, fp32 result) with the HIP
     vector-Jacobian product as its backward; a bf16 input gets its gradient in bf16."""

@@ -33,6 +33,8 @@ luma_transfer           -- (colour-preserving recombination)         --
 resize_labels           -- (nearest resize of uint8 label maps)      --
 region_stats            -- (masked per-region channel statistics)    --
 adain_regions           -- (regional multi-style AdaIN)              --
+efdm                    -- (exact feature distribution matching)     d content = grad (straight-through)
+plane_sort              -- (segmented totalOrder sort of planes)     --
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -685,7 +687,40 @@ def _(content, labels, style_mean, style_std, mix, alpha, swap_style_stats):
     return torch.empty_like(content)
 
 
+# ------------------------------------------------------------------------------------------------
+# Exact feature distribution matching and the plane sort (csrc/efdm.hip)
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::efdm", mutates_args=())
+def efdm(content: Tensor, style: Tensor, alpha: float) -> Tensor:
+    """Rank r of every content plane takes the style plane's sorted value S[j(r)] (+ alpha blend)."""
+    return ops.efdm(content, style, alpha=alpha)
+
+
+@register_fake("ast_hip::efdm")
+def _(content, style, alpha):
+    return torch.empty_like(content)
+
+
+def _efdm_backward(ctx, g):   # straight-through: d content = grad_out, none for the style; no kernel
+    return g, None, None
+
+
+register_autograd("ast_hip::efdm", _efdm_backward)
+
+
+@custom_op("ast_hip::plane_sort", mutates_args=())
+def plane_sort(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """Every plane sorted in IEEE totalOrder, ties in index order: (values, int32 indices)."""
+    return ops.plane_sort(x, return_index=True)
+
+
+@register_fake("ast_hip::plane_sort")
+def _(x):
+    return torch.empty_like(x), x.new_empty(x.shape, dtype=torch.int32)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions"]
+                  "region_stats", "adain_regions", "efdm", "plane_sort"]

@@ -61,7 +61,8 @@ def _pair(x, y, what):
 __all__ = ["gram_matrix", "compute_content_loss", "compute_style_loss", "tv_loss", "compute_hist_loss",
            "content_mvn_loss", "style_loss_weighted", "content_style_loss", "EarthMoversDistanceLoss",
            "HistLayerBase",
-           "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss"]
+           "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss",
+           "compute_efdm_loss"]
 
 
 def gram_matrix(tensor):
@@ -153,6 +154,17 @@ def compute_hist_loss(t_cs, style_map, weight: float = 1.0):
     if x.shape[0] != y.shape[0]:
         raise Fn.HipOpError(f"hist loss: batch mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
     return _two_sided(lambda a, b: _ops.hist_loss(a, b, float(weight))[0], x, y)
+
+
+def compute_efdm_loss(t_cs_map, style_map, weight: float = 1.0):
+    """The EFDM style loss of one loss tap (Zhang et al., CVPR 2022): weight * mean((f - efdm(f, s))^2)
+    with the matched target detached, so the gradient is 2 * weight * (f - target) / numel and none
+    reaches the style. The target is Fn.EFDMFn at alpha = 1 under no_grad (the style values, bit for
+    bit), the mean is the sqdiff kernel (Fn.SqDiffMeanFn)."""
+    x, y = _dev(t_cs_map, "t_cs_map"), _dev(style_map, "style_map")
+    with torch.no_grad():
+        target = Fn.EFDMFn.apply(x, y, 1.0)
+    return Fn.SqDiffMeanFn.apply(x, target, float(weight))
 
 
 def out_of_range_loss(img, weight: float = 1e8):

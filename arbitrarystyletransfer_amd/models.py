@@ -46,6 +46,21 @@ class AdaIN(nn.Module):
         return ops.adain(content_map, style_map, alpha=alpha, swap_style_stats=not self.canonical)
 
 
+class EFDM(nn.Module):
+    """Exact feature distribution matching (Zhang et al., CVPR 2022) as a drop-in for the AdaIN
+    layer: every content channel keeps its spatial ordering and takes the style channel's whole
+    empirical distribution (ops.efdm; the reference has no counterpart). `alpha` fuses the blend
+    c + alpha * (t - c). Under autograd the gradient passes straight through to the content
+    (Fn.EFDMFn); none reaches the style. No parameters."""
+
+    def forward(self, content_map, style_map, alpha: float = 1.0):
+        if _compiling():
+            return _ops().efdm(content_map, style_map, float(alpha))
+        if torch.is_grad_enabled() and (content_map.requires_grad or style_map.requires_grad):
+            return Fn.EFDMFn.apply(content_map, style_map, float(alpha))
+        return ops.efdm(content_map, style_map, alpha=alpha)
+
+
 def calc_mean_std(feat, eps=1e-5):
     """models.py:54-62: per-(n,c) mean and sqrt(unbiased var + eps)."""
     if feat.dim() != 4:
@@ -386,13 +401,27 @@ class AdaINStyleTransfer(nn.Module):
     style batches of the same shape are encoded in the same launches. `preserve_color=True`
     (inference only) keeps the content image's colours: the result is ops.luma_transfer(decoder
     output, content_img), the stylised Lab luminance with the content's a and b.
+    `transform="efdm"` puts exact feature distribution matching (EFDM) in AdaIN's place, under the
+    same attribute name `adain` (what AdaINTrainer calls); the statistics-based methods
+    (style_statistics, stylize_with_stats, stylize_regions) then raise NotImplementedError.
     """
 
-    def __init__(self, canonical: bool = False, enc_seed: int = 1, dec_seed: int = 2, weights="live"):
+    TRANSFORMS = ("adain", "efdm")
+
+    def __init__(self, canonical: bool = False, enc_seed: int = 1, dec_seed: int = 2, weights="live",
+                 transform: str = "adain"):
         super().__init__()
+        if transform not in self.TRANSFORMS:
+            raise ValueError(f"transform must be one of {self.TRANSFORMS}, got {transform!r}")
+        self.transform = transform
         self.encoder = PretrainedEncoder(content_layers=["relu_9"], weights=weights, seed=enc_seed)
-        self.adain = AdaIN(canonical=canonical)
+        self.adain = AdaIN(canonical=canonical) if transform == "adain" else EFDM()
         self.decoder = VGGDecoder(weights=weights, seed=dec_seed)
+
+    def _needs_statistics(self, what):
+        if self.transform != "adain":
+            raise NotImplementedError(f"{what} works on per-channel mean and std, which transform="
+                                      f"{self.transform!r} does not use; build the model with transform='adain'")
 
     def encode_pair(self, content_img, style_img):
         if content_img.shape[1:] == style_img.shape[1:]:
@@ -420,6 +449,7 @@ class AdaINStyleTransfer(nn.Module):
     #    broadcasts its relu4_1 statistics (dp.broadcast_style_stats, 2*512 floats) --------------
     def style_statistics(self, style_img):
         """(mean, std) of the style's relu4_1 features, each [N_style, 512]."""
+        self._needs_statistics("style_statistics")
         f_s = self.encoder(style_img)[0]
         m, s = channel_stats(f_s)
         return m.flatten(1), s.flatten(1)
@@ -428,6 +458,7 @@ class AdaINStyleTransfer(nn.Module):
                            preserve_color: bool = False):
         """Stylise a content batch with given style statistics ([512] shared, or [N, 512]);
         preserve_color as in forward."""
+        self._needs_statistics("stylize_with_stats")
         if torch.is_grad_enabled() and (content_img.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_with_stats is inference-only; run it under torch.no_grad()")
         f_c = self.encoder(content_img)[0]
@@ -452,6 +483,7 @@ class AdaINStyleTransfer(nn.Module):
         style_labels: uint8 [S, Hs, Ws] with the same region ids: region k then takes the
         statistics of each style's own region k instead of the whole style map (K * S <= 64).
         preserve_color as in forward."""
+        self._needs_statistics("stylize_regions")
         if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
                                         or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_regions is inference-only; run it under torch.no_grad()")

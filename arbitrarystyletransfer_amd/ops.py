@@ -388,6 +388,67 @@ def adain_regions(content: torch.Tensor, labels: torch.Tensor, style_mean: torch
     return out
 
 
+# Exact feature distribution matching and the plane sort (csrc/efdm.hip): AST_EFDM_FUSED_MAX of ast_hip.h,
+# the largest plane (of either map) that the one-launch, no-workspace path takes
+EFDM_FUSED_MAX = 16384
+
+
+def _ws_bytes(nbytes: int, what: str, device):
+    """The device workspace of a *_workspace_bytes query (None for 0; a negative query is its error)."""
+    if nbytes < 0:
+        check(int(nbytes), what)
+    return torch.empty((int(nbytes),), device=device, dtype=torch.uint8) if nbytes else None
+
+
+def efdm(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, _chunk: int = 0):
+    """Exact feature distribution matching (Zhang et al., CVPR 2022), a drop-in for adain: in every
+    (n, c) plane the content element of rank r (stable ascending, floats in IEEE totalOrder of
+    their bits) takes the style plane's sorted value S[((2r + 1) * Ms) // (2 * Mc)]. At alpha == 1
+    every output is a copy of a style value; otherwise c + alpha * (t - c).
+    content [N, C, Hc, Wc]; style [N, C, Hs, Ws] or [1, C, Hs, Ws] (shared by the batch).
+    _chunk (tests): a power of two >= 64 forces the chunk-sort + merge path with that LDS chunk."""
+    content = _dev(content, "content_map")
+    style = _dev(style, "style_map")
+    if (content.dim() != 4 or style.dim() != 4 or content.shape[1] != style.shape[1]
+            or style.shape[0] not in (1, content.shape[0]) or content.numel() == 0 or style.numel() == 0):
+        raise HipOpError(f"EFDM needs non-empty NCHW maps with equal C and a style batch of N or 1: "
+                         f"{tuple(content.shape)} vs {tuple(style.shape)}")
+    if style.device != content.device:
+        raise HipOpError(f"style_map is on {style.device}, content_map on {content.device}")
+    n, c, hc, wc = (int(s) for s in content.shape)
+    ns, hs, ws = int(style.shape[0]), int(style.shape[2]), int(style.shape[3])
+    L = lib()
+    nbytes = int(L.ast_efdm_ex_workspace_bytes(n, ns, c, hc * wc, hs * ws, int(_chunk)))
+    wsb = _ws_bytes(nbytes, "efdm workspace", content.device)
+    out = torch.empty_like(content)
+    algo = 4 * (2 * content.numel() + n * c * hs * ws)   # algorithmic: read c, read s, write out
+    check(_timed(f"efdm {c}ch {hc}x{wc}", -algo, content.device, lambda: L.ast_efdm_ex_f32(
+        ptr(content), ptr(style), ptr(out), n, ns, c, hc, wc, hs, ws, float(alpha), int(_chunk), ptr(wsb),
+        max(nbytes, 0), stream_ptr(content.device))), "efdm")
+    return out
+
+
+def plane_sort(x: torch.Tensor, return_index: bool = False, _chunk: int = 0):
+    """Every plane of x (all dimensions after the first two flattened; a 2-D x is [planes, M])
+    sorted ascending in IEEE totalOrder of the bits (-0 < +0, negative NaNs first, positive NaNs
+    last), ties in index order: the sorted values in x's shape and, with return_index, the int32
+    index of each value within its plane."""
+    x = _dev(x, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise HipOpError(f"plane_sort needs a non-empty [planes, M] or [N, C, ...] tensor, got {tuple(x.shape)}")
+    planes = int(x.shape[0]) if x.dim() == 2 else int(x.shape[0] * x.shape[1])
+    m = x.numel() // planes
+    L = lib()
+    nbytes = int(L.ast_plane_sort_workspace_bytes(planes, m, 1 if return_index else 0, int(_chunk)))
+    wsb = _ws_bytes(nbytes, "plane_sort workspace", x.device)
+    vals = torch.empty_like(x)
+    index = torch.empty(x.shape, device=x.device, dtype=torch.int32) if return_index else None
+    check(_timed(f"plane_sort {planes}x{m}", -8 * x.numel(), x.device, lambda: L.ast_plane_sort_f32(
+        ptr(x), ptr(vals), ptr(index), planes, m, int(_chunk), ptr(wsb), max(nbytes, 0), stream_ptr(x.device))),
+        "plane_sort")
+    return (vals, index) if return_index else vals
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

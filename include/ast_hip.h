@@ -167,6 +167,44 @@ int ast_adain_regions_f32(const float* content, const unsigned char* labels,
                           int mix_stride_n /* 0: one mix for the batch, else regions*rows */,
                           double alpha, int swap_style_stats, void* stream);
 
+/* Exact feature distribution matching (EFDM, Zhang et al. CVPR 2022; csrc/efdm.hip; an extension,
+ * no reference counterpart) and the segmented plane sort under it.
+ * Order: IEEE-754 totalOrder of the bits -- as a signed integer key = b < 0 ? -(b & 0x7fffffff) - 1
+ * : b for the int32 view b -- so -0 < +0, negative NaNs first, positive NaNs last, and equal keys
+ * are equal bits. Ties keep index order (a stable ascending sort).
+ * For every plane (n, ch), Mc = hc*wc, Ms = hs*ws: r(i) = the stable rank of content element i,
+ * S = the style plane's values in ascending order, j(r) = ((2r + 1) * Ms) / (2 * Mc) in 64-bit
+ * integers (the identity when Ms == Mc), t[i] = S[j(r(i))], and
+ *   out[i] = t[i]                           when alpha == 1 (the style value's bits, no arithmetic),
+ *   out[i] = c[i] + alpha * (t[i] - c[i])   otherwise, in fp32.
+ * content, out [n, c, hc, wc]; style [ns, c, hs, ws] with ns == n, or ns == 1 (one style shared by
+ * the batch). Planes of at most AST_EFDM_FUSED_MAX elements (both maps) run in one launch with no
+ * workspace; anything larger, up to 2^31 - 1 elements per plane, sorts chunks in LDS and merges
+ * them through `workspace` (device memory, 4-byte aligned, ast_efdm_workspace_bytes bytes; may be
+ * NULL when that is 0). No host synchronisation, no atomics: bitwise reproducible, capturable.
+ * The _ex form takes the LDS chunk length of the general path: 0 = automatic (what the plain entry
+ * passes), else a power of two in 64..AST_EFDM_FUSED_MAX (AST_E_UNSUPPORTED otherwise), which
+ * forces the general path at any size; its workspace is ast_efdm_ex_workspace_bytes with the same
+ * chunk. AST_E_SHAPE: a size <= 0, ns not in {1, n}, a plane over 2^31 - 1 or a map over 2^40
+ * elements, or a workspace smaller than the query. The workspace queries return the same negative codes for bad arguments. */
+#define AST_EFDM_FUSED_MAX 16384
+long long ast_efdm_workspace_bytes(int n, int ns, int c, long long mc, long long ms);
+long long ast_efdm_ex_workspace_bytes(int n, int ns, int c, long long mc, long long ms, int chunk);
+int ast_efdm_f32(const float* content, const float* style, float* out, int n, int ns, int c,
+                 int hc, int wc, int hs, int ws, double alpha, void* workspace,
+                 long long workspace_bytes, void* stream);
+int ast_efdm_ex_f32(const float* content, const float* style, float* out, int n, int ns, int c,
+                    int hc, int wc, int hs, int ws, double alpha, int chunk, void* workspace,
+                    long long workspace_bytes, void* stream);
+
+/* The segmented sort on its own: every row of x [planes, m] in the order above, as values
+ * (`sorted`) and, when index_or_null is given, the int32 source index of each (ties in index
+ * order). chunk and workspace as ast_efdm_ex_f32; the query takes want_index (0/1). */
+long long ast_plane_sort_workspace_bytes(long long planes, long long m, int want_index, int chunk);
+int ast_plane_sort_f32(const float* x, float* sorted, int* index_or_null, long long planes,
+                       long long m, int chunk, void* workspace, long long workspace_bytes,
+                       void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
