@@ -47,6 +47,15 @@ SIGNATURES = {
     "ast_efdm_ex_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _ll, _p]),
     "ast_plane_sort_workspace_bytes": (_ll, [_ll, _ll, _i, _i]),
     "ast_plane_sort_f32": (_i, [_p, _p, _p, _ll, _ll, _i, _p, _ll, _p]),
+    "ast_wct_default_iters": (_i, [_i, _f]),
+    "ast_wct_cov_workspace_bytes": (_ll, [_i, _i, _ll]),
+    "ast_wct_cov_f32": (_i, [_p, _p, _p, _i, _i, _ll, _f, _p, _ll, _p]),
+    "ast_wct_sqrt_workspace_bytes": (_ll, [_i, _i]),
+    "ast_wct_sqrt_f32": (_i, [_p, _p, _p, _i, _i, _i, _p, _ll, _p]),
+    "ast_wct_apply_workspace_bytes": (_ll, [_i, _i]),
+    "ast_wct_apply_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _d, _p, _ll, _p]),
+    "ast_wct_workspace_bytes": (_ll, [_i, _i, _i, _ll, _ll]),
+    "ast_wct_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _f, _i, _p, _ll, _p]),
     "ast_conv3x3_pack_weights_ex_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ast_conv_act_backward_f32": (_i, [_p, _p, _p, _p, _p, _ll, _i, _i, _p]),
     "ast_relu_mask_f32": (_i, [_p, _p, _p, _ll, _p]),

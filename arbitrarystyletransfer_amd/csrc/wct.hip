@@ -1,0 +1,511 @@
+// Whitening and colouring transform (WCT; Li et al., NeurIPS 2017) for gfx950, fp32 storage. The
+// definition is in include/ast_hip.h; tests/wct_ref.py restates it. Three stages, each a C-ABI entry
+// of its own, and ast_wct_f32 is exactly their composition:
+//   covariance    plane means (shifted one-pass sum, exact for a constant plane), then the centred
+//                 product (x - mu)(x - mu)^T over the upper-triangle tiles only, split along the
+//                 pixels; the partial tiles meet in a workspace and are summed in split order, scaled
+//                 by 1/(M - 1), mirrored into the lower triangle, and the ridge goes on the diagonal
+//   roots         coupled Newton-Schulz: per iteration P = 1.5 I - 0.5 Z Y (epilogue fused), then
+//                 [Y; Z] <- [Y P; P Z] as one launch of 2 * batch products between two buffers
+//   apply         T = S^(1/2)_style . S^(-1/2)_content, then out = alpha (T (x - mu_c) + mu_s) +
+//                 (1 - alpha) x as one GEMM with the centring staged into the operand and the bias
+//                 and blend in the epilogue
+// Every product is v_mfma_f32_32x32x2_f32 on fp32 operands (the tile of mbtrain.hip's gemm_kernel:
+// 64x64 per workgroup, 4 waves x 32x32, K in chunks of 32 through LDS with the next chunk's loads in
+// flight). Tiles past a matrix edge are zero-filled while staging, so any C in 1..1024 and any
+// plane size run the same code. No atomics, no host synchronisation, no allocation: every sample is
+// indexed by a grid dimension, so a non-finite value stays inside its own sample.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "../../include/ast_hip.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kT = 256;                 // threads per workgroup everywhere in this file
+constexpr int WT = 64, WK = 32, WP = WT + 1, WL = WK * WT / kT;
+constexpr int kMaxC = 1024;
+constexpr int kMaxSplits = 8;           // covariance K splits per sample
+constexpr float kTraceFloor = 1e-20f;
+
+// Sum / max of v over the workgroup in a fixed order; every thread receives the result.
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < kT / 64; ++i) t += sh[i];
+  return t;
+}
+
+__device__ __forceinline__ float block_max(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int i = 1; i < kT / 64; ++i) t = fmaxf(t, sh[i]);
+  return t;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One 64x64 tile of (A - amu) . (B - bmu) over k in [kbeg, kend), as this wave's 32x32 accumulator.
+// A is k-contiguous: A(m, k) = A[m * lda + k]. B is either k-contiguous as well (BKFAST, B(k, n) =
+// B[n * ldb + k]: the covariance, whose second operand is the first one transposed) or
+// n-contiguous (B(k, n) = B[k * ldb + n]). amu / bmu (null: none) are indexed by the operand's row
+// in memory -- m for A, n for a k-contiguous B, k for an n-contiguous one -- and are subtracted while
+// staging; elements past M, N or kend are staged as 0, not as -mu.
+// Accumulator element i of a lane is row wm * 32 + (i & 3) + 8 (i >> 2) + 4 h, column wn * 32 + r.
+// ------------------------------------------------------------------------------------------------
+template <bool BKFAST>
+__device__ __forceinline__ f32x16 tile_mm(const float* __restrict__ A, int64_t lda, const float* __restrict__ amu,
+                                          const float* __restrict__ B, int64_t ldb, const float* __restrict__ bmu,
+                                          int M, int N, int m0, int n0, int kbeg, int kend, float* As, float* Bs) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int k_f = tid & 31, r_f = tid >> 5;  // k-contiguous operand: k = k_f, row = r_f + 8 i
+  const int n_f = tid & 63, k_s = tid >> 6;  // n-contiguous B: column n_f, k = k_s + 4 i
+  float ra[WL], rb[WL], am[WL], bm[WL];
+#pragma unroll
+  for (int i = 0; i < WL; ++i) {
+    const int gm = m0 + r_f + 8 * i, gn = n0 + r_f + 8 * i;
+    am[i] = (amu && gm < M) ? amu[gm] : 0.f;
+    bm[i] = (BKFAST && bmu && gn < N) ? bmu[gn] : 0.f;
+  }
+  auto load = [&](int k0) {
+    const int gk = k0 + k_f;
+#pragma unroll
+    for (int i = 0; i < WL; ++i) {
+      const int gm = m0 + r_f + 8 * i;
+      ra[i] = (gk < kend && gm < M) ? A[(int64_t)gm * lda + gk] - am[i] : 0.f;
+    }
+    if (BKFAST) {
+#pragma unroll
+      for (int i = 0; i < WL; ++i) {
+        const int gn = n0 + r_f + 8 * i;
+        rb[i] = (gk < kend && gn < N) ? B[(int64_t)gn * ldb + gk] - bm[i] : 0.f;
+      }
+    } else {
+      const int gn = n0 + n_f;
+#pragma unroll
+      for (int i = 0; i < WL; ++i) {
+        const int gk2 = k0 + k_s + 4 * i;
+        rb[i] = (gk2 < kend && gn < N) ? B[(int64_t)gk2 * ldb + gn] - (bmu ? bmu[gk2] : 0.f) : 0.f;
+      }
+    }
+  };
+  f32x16 acc = (f32x16){0.f};
+  if (kbeg < kend) load(kbeg);
+  for (int k0 = kbeg; k0 < kend; k0 += WK) {
+#pragma unroll
+    for (int i = 0; i < WL; ++i) {
+      As[k_f * WP + r_f + 8 * i] = ra[i];
+      if (BKFAST) Bs[k_f * WP + r_f + 8 * i] = rb[i];
+      else Bs[(k_s + 4 * i) * WP + n_f] = rb[i];
+    }
+    __syncthreads();
+    if (k0 + WK < kend) load(k0 + WK);
+#pragma unroll
+    for (int kp = 0; kp < WK / 2; ++kp)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(2 * kp + h) * WP + wm * 32 + r], Bs[(2 * kp + h) * WP + wn * 32 + r],
+                                                 acc, 0, 0, 0);
+    __syncthreads();
+  }
+  return acc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Covariance
+// ------------------------------------------------------------------------------------------------
+
+// mean[p] of plane p: x0 + sum(x - x0) / M with x0 the plane's first element, so a constant plane
+// has exactly its value as mean (its centred values, trace and covariance are then exactly 0).
+__global__ __launch_bounds__(kT) void wct_mean_kernel(const float* __restrict__ x, float* __restrict__ mean, int64_t M) {
+  __shared__ float sh[kT / 64];
+  const float* p = x + (int64_t)blockIdx.x * M;
+  const float x0 = p[0];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < M; i += kT) s += p[i] - x0;
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) mean[blockIdx.x] = x0 + s / (float)M;
+}
+
+// grid (upper-triangle tile pairs, K splits, samples): one dense 64x64 partial tile each.
+__global__ __launch_bounds__(kT) void wct_cov_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                    float* __restrict__ part, int C, int64_t M, int kchunk) {
+  __shared__ float As[WK * WP];
+  __shared__ float Bs[WK * WP];
+  int p = blockIdx.x, ti = 0, rowlen = (C + WT - 1) / WT;
+  while (p >= rowlen) {
+    p -= rowlen;
+    ++ti;
+    --rowlen;
+  }
+  const int tj = ti + p;
+  const int b = blockIdx.z, ks = blockIdx.y;
+  const int kbeg = ks * kchunk, kend = (int)min((int64_t)kbeg + kchunk, M);
+  const float* X = x + (int64_t)b * C * M;
+  const float* mu = mean + (int64_t)b * C;
+  const f32x16 acc = tile_mm<true>(X, M, mu, X, M, mu, C, C, ti * WT, tj * WT, kbeg, kend, As, Bs);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int wm = wave & 1, wn = wave >> 1;
+  float* P = part + (((int64_t)b * gridDim.y + ks) * gridDim.x + blockIdx.x) * (WT * WT) + wn * 32 + r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) P[(wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * WT] = acc[i];
+}
+
+// grid (tile pairs, samples): the splits of every element in split order, / (M - 1), written to
+// (i, j) and (j, i) from the same register; a diagonal tile keeps its i <= j half.
+__global__ __launch_bounds__(kT) void wct_cov_reduce_kernel(const float* __restrict__ part, float* __restrict__ cov,
+                                                           int C, int splits, float denom) {
+  int p = blockIdx.x, ti = 0, rowlen = (C + WT - 1) / WT;
+  while (p >= rowlen) {
+    p -= rowlen;
+    ++ti;
+    --rowlen;
+  }
+  const int tj = ti + p, b = blockIdx.y;
+  const int64_t tile = WT * WT, sstride = (int64_t)gridDim.x * tile;
+  const float* P = part + (int64_t)b * splits * sstride + (int64_t)blockIdx.x * tile;
+  float* S = cov + (int64_t)b * C * C;
+  for (int e = threadIdx.x; e < WT * WT; e += kT) {
+    const int i = ti * WT + e / WT, j = tj * WT + e % WT;
+    if (i >= C || j >= C || (ti == tj && i > j)) continue;
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += P[k * sstride + e];
+    s /= denom;
+    S[(int64_t)i * C + j] = s;
+    S[(int64_t)j * C + i] = s;
+  }
+}
+
+// grid (samples): eps = eps_rel * max(tr / C, floor) on the C real diagonal entries.
+__global__ __launch_bounds__(kT) void wct_ridge_kernel(float* __restrict__ cov, int C, float eps_rel) {
+  __shared__ float sh[kT / 64];
+  float* S = cov + (int64_t)blockIdx.x * C * C;
+  float t = 0.f;
+  for (int i = threadIdx.x; i < C; i += kT) t += S[(int64_t)i * C + i];
+  t = block_sum(t, sh);
+  const float eps = eps_rel * fmaxf(t / (float)C, kTraceFloor);
+  for (int i = threadIdx.x; i < C; i += kT) S[(int64_t)i * C + i] += eps;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Newton-Schulz
+// ------------------------------------------------------------------------------------------------
+
+// grid (matrices): norm[b] = ||S||_F as max|s| * sqrt(sum (s / max|s|)^2), so neither a tiny matrix
+// (the 1e-23 ridge of a constant map) nor a huge one leaves the fp32 range under the square.
+__global__ __launch_bounds__(kT) void wct_norm_kernel(const float* __restrict__ cov, float* __restrict__ norm, int C) {
+  __shared__ float sh[kT / 64];
+  const int64_t cc = (int64_t)C * C;
+  const float* S = cov + (int64_t)blockIdx.x * cc;
+  float m = 0.f;
+  for (int64_t i = threadIdx.x; i < cc; i += kT) m = fmaxf(m, fabsf(S[i]));
+  m = block_max(m, sh);
+  __syncthreads();
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < cc; i += kT) {
+    const float v = S[i] / m;
+    s += v * v;
+  }
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) norm[blockIdx.x] = m * sqrtf(s);
+}
+
+// grid (elements / 256, matrices): Y0 = S / ||S||_F, Z0 = I.
+__global__ __launch_bounds__(kT) void wct_ns_init_kernel(const float* __restrict__ cov, const float* __restrict__ norm,
+                                                        float* __restrict__ Y, float* __restrict__ Z, int C) {
+  const int64_t cc = (int64_t)C * C, e = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (e >= cc) return;
+  const int64_t o = (int64_t)blockIdx.y * cc + e;
+  Y[o] = cov[o] / norm[blockIdx.y];
+  Z[o] = (e / C == e % C) ? 1.f : 0.f;
+}
+
+// grid (elements / 256, matrices): S^(1/2) = Y sqrt(||S||_F), S^(-1/2) = Z / sqrt(||S||_F).
+__global__ __launch_bounds__(kT) void wct_ns_final_kernel(const float* __restrict__ Y, const float* __restrict__ Z,
+                                                         const float* __restrict__ norm, float* __restrict__ root,
+                                                         float* __restrict__ iroot, int C) {
+  const int64_t cc = (int64_t)C * C, e = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (e >= cc) return;
+  const int64_t o = (int64_t)blockIdx.y * cc + e;
+  const float q = sqrtf(norm[blockIdx.y]);
+  if (root) root[o] = Y[o] * q;
+  if (iroot) iroot[o] = Z[o] / q;
+}
+
+// Batched square products of C x C row-major matrices, grid (tiles, tiles, products).
+//   kStepP   P[z] = 1.5 I - 0.5 Z[z] Y[z]                        (yz = [Y; Z], `batch` of each)
+//   kStepYZ  z < batch: Yn[z] = Y[z] P[z];  else Zn[z'] = P[z'] Z[z'], z' = z - batch
+//   kPlain   out[z] = A[z * sA] B[z * sB]                         (T = S^(1/2)_style S^(-1/2)_content)
+enum { kStepP = 0, kStepYZ = 1, kPlain = 2 };
+
+template <int MODE>
+__global__ __launch_bounds__(kT) void wct_sq_gemm_kernel(const float* __restrict__ a0, const float* __restrict__ b0,
+                                                        float* __restrict__ out, int64_t sA, int64_t sB, int C,
+                                                        int batch) {
+  __shared__ float As[WK * WP];
+  __shared__ float Bs[WK * WP];
+  const int64_t cc = (int64_t)C * C;
+  const int z = blockIdx.z;
+  const float *A, *B;
+  if (MODE == kStepP) {          // a0 = [Y; Z]
+    A = a0 + (int64_t)(batch + z) * cc;
+    B = a0 + (int64_t)z * cc;
+  } else if (MODE == kStepYZ) {  // a0 = [Y; Z], b0 = P
+    if (z < batch) {
+      A = a0 + (int64_t)z * cc;
+      B = b0 + (int64_t)z * cc;
+    } else {
+      A = b0 + (int64_t)(z - batch) * cc;
+      B = a0 + (int64_t)z * cc;
+    }
+  } else {
+    A = a0 + (int64_t)z * sA;
+    B = b0 + (int64_t)z * sB;
+  }
+  const int m0 = blockIdx.y * WT, n0 = blockIdx.x * WT;
+  const f32x16 acc = tile_mm<false>(A, C, nullptr, B, C, nullptr, C, C, m0, n0, 0, C, As, Bs);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int n = n0 + (wave >> 1) * 32 + r;
+  if (n >= C) return;
+  float* O = out + (int64_t)z * cc + n;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int m = m0 + (wave & 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+    if (m >= C) continue;
+    O[(int64_t)m * C] = MODE == kStepP ? (m == n ? 1.5f : 0.f) - 0.5f * acc[i] : acc[i];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Apply: out[b] = alpha (T[b] (x[b] - mu_c[b]) + mu_s[b']) + (1 - alpha) x[b], grid (pixel tiles,
+// channel tiles, samples); b' = b, or 0 for a shared style (smu_stride = 0).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kT) void wct_apply_kernel(const float* __restrict__ T, const float* __restrict__ x,
+                                                      const float* __restrict__ cmu, const float* __restrict__ smu,
+                                                      float* __restrict__ out, int C, int64_t M, int64_t smu_stride,
+                                                      float alpha) {
+  __shared__ float As[WK * WP];
+  __shared__ float Bs[WK * WP];
+  const int b = blockIdx.z;
+  const float* X = x + (int64_t)b * C * M;
+  const float* Tb = T + (int64_t)b * C * C;
+  const int m0 = blockIdx.y * WT, n0 = blockIdx.x * WT;
+  const f32x16 acc = tile_mm<false>(Tb, C, nullptr, X, M, cmu + (int64_t)b * C, C, (int)M, m0, n0, 0, C, As, Bs);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t n = n0 + (wave >> 1) * 32 + r;
+  if (n >= M) return;
+  const float* ms = smu + (int64_t)b * smu_stride;
+  float* O = out + (int64_t)b * C * M + n;
+  const float beta = 1.f - alpha;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int m = m0 + (wave & 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+    if (m >= C) continue;
+    const float t = acc[i] + ms[m];
+    O[(int64_t)m * M] = alpha * t + beta * X[(int64_t)m * M + n];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side: argument checks, workspace layouts, launch sequences
+// ------------------------------------------------------------------------------------------------
+
+inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+inline bool eps_ok(float e) { return e >= 1e-4f && e <= 1.f; }
+inline int tiles_of(int c) { return (c + WT - 1) / WT; }
+
+// K split of the covariance: chunks of at least 64 pixels (a multiple of 32), at most kMaxSplits.
+inline int cov_splits(int64_t m, int* kchunk) {
+  int64_t s = (m + 63) / 64;
+  if (s > kMaxSplits) s = kMaxSplits;
+  const int64_t kc = (((m + s - 1) / s) + 31) / 32 * 32;
+  if (kchunk) *kchunk = (int)kc;
+  return (int)((m + kc - 1) / kc);
+}
+
+inline int default_iters(int c, float eps_rel) {
+  return (int)ceil(log((double)c / (double)eps_rel) / log(2.25)) + 5;
+}
+
+// AST_OK, or the code that rejects (samples, channels, pixels per plane)
+inline int cov_shape(int n, int c, int64_t m) {
+  if (n <= 0 || c <= 0 || m < 2 || m > 0x7fffffffLL || n > 32767) return AST_E_SHAPE;
+  if (c > kMaxC) return AST_E_UNSUPPORTED;
+  return AST_OK;
+}
+
+inline int64_t cov_ws(int n, int c, int64_t m) {
+  const int t = tiles_of(c);
+  return al256((int64_t)4 * n * cov_splits(m, nullptr) * (t * (t + 1) / 2) * (WT * WT));
+}
+
+inline int64_t sqrt_ws(int b, int c) { return al256((int64_t)4 * b) + 5 * al256((int64_t)4 * b * c * c); }
+inline int64_t apply_ws(int n, int c) { return al256((int64_t)4 * n * c * c); }
+
+int cov_launch(const float* x, float* mean, float* cov, int n, int c, int64_t m, float eps_rel, float* part,
+               hipStream_t st) {
+  int kchunk = 0;
+  const int splits = cov_splits(m, &kchunk), t = tiles_of(c), pairs = t * (t + 1) / 2;
+  hipLaunchKernelGGL(wct_mean_kernel, dim3((unsigned)(n * c)), dim3(kT), 0, st, x, mean, m);
+  hipLaunchKernelGGL(wct_cov_kernel, dim3(pairs, splits, n), dim3(kT), 0, st, x, (const float*)mean, part, c, m, kchunk);
+  hipLaunchKernelGGL(wct_cov_reduce_kernel, dim3(pairs, n), dim3(kT), 0, st, (const float*)part, cov, c, splits,
+                     (float)(m - 1));
+  hipLaunchKernelGGL(wct_ridge_kernel, dim3(n), dim3(kT), 0, st, cov, c, eps_rel);
+  return (int)hipGetLastError();
+}
+
+int sqrt_launch(const float* cov, float* root, float* iroot, int b, int c, int iters, unsigned char* ws,
+                hipStream_t st) {
+  const int64_t mb = al256((int64_t)4 * b * c * c);
+  float* norm = (float*)ws;
+  float* yz[2] = {(float*)(ws + al256((int64_t)4 * b)), (float*)(ws + al256((int64_t)4 * b) + 2 * mb)};
+  float* P = (float*)(ws + al256((int64_t)4 * b) + 4 * mb);
+  const int64_t cc = (int64_t)c * c;
+  const int t = tiles_of(c);
+  const dim3 eg((unsigned)((cc + kT - 1) / kT), b);
+  hipLaunchKernelGGL(wct_norm_kernel, dim3(b), dim3(kT), 0, st, cov, norm, c);
+  hipLaunchKernelGGL(wct_ns_init_kernel, eg, dim3(kT), 0, st, cov, (const float*)norm, yz[0], yz[0] + b * cc, c);
+  int cur = 0;
+  for (int it = 0; it < iters; ++it, cur ^= 1) {
+    hipLaunchKernelGGL(wct_sq_gemm_kernel<kStepP>, dim3(t, t, b), dim3(kT), 0, st, (const float*)yz[cur],
+                       (const float*)nullptr, P, (int64_t)0, (int64_t)0, c, b);
+    hipLaunchKernelGGL(wct_sq_gemm_kernel<kStepYZ>, dim3(t, t, 2 * b), dim3(kT), 0, st, (const float*)yz[cur],
+                       (const float*)P, yz[cur ^ 1], (int64_t)0, (int64_t)0, c, b);
+  }
+  hipLaunchKernelGGL(wct_ns_final_kernel, eg, dim3(kT), 0, st, (const float*)yz[cur], (const float*)(yz[cur] + b * cc),
+                     (const float*)norm, root, iroot, c);
+  return (int)hipGetLastError();
+}
+
+int apply_launch(const float* content, const float* cmu, const float* smu, const float* sroot, const float* ciroot,
+                 float* out, int n, int ns, int c, int64_t mc, float alpha, float* T, hipStream_t st) {
+  const int64_t cc = (int64_t)c * c;
+  const int t = tiles_of(c);
+  hipLaunchKernelGGL(wct_sq_gemm_kernel<kPlain>, dim3(t, t, n), dim3(kT), 0, st, sroot, ciroot, T,
+                     ns == 1 ? (int64_t)0 : cc, cc, c, n);
+  hipLaunchKernelGGL(wct_apply_kernel, dim3((unsigned)((mc + WT - 1) / WT), t, n), dim3(kT), 0, st, (const float*)T,
+                     content, cmu, smu, out, c, mc, ns == 1 ? (int64_t)0 : (int64_t)c, alpha);
+  return (int)hipGetLastError();
+}
+
+int pair_shape(int n, int ns, int c, int64_t mc, int64_t ms) {
+  if (n <= 0 || ns <= 0 || (ns != n && ns != 1)) return AST_E_SHAPE;
+  int e = cov_shape(n, c, mc);
+  if (e) return e;
+  e = cov_shape(ns, c, ms);
+  if (e) return e;
+  return n + ns > 32767 ? AST_E_SHAPE : AST_OK;
+}
+
+inline int64_t max3(int64_t a, int64_t b, int64_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+
+}  // namespace
+
+extern "C" {
+
+int ast_wct_default_iters(int c, float eps_rel) {
+  if (c <= 0) return AST_E_SHAPE;
+  if (c > kMaxC || !eps_ok(eps_rel)) return AST_E_UNSUPPORTED;
+  return default_iters(c, eps_rel);
+}
+
+long long ast_wct_cov_workspace_bytes(int n, int c, long long m) {
+  const int e = cov_shape(n, c, m);
+  return e ? e : cov_ws(n, c, m);
+}
+
+int ast_wct_cov_f32(const float* x, float* mean, float* cov, int n, int c, long long m, float eps_rel, void* workspace,
+                    long long workspace_bytes, void* stream) {
+  if (!x || !mean || !cov || !workspace) return AST_E_NULLPTR;
+  const int e = cov_shape(n, c, m);
+  if (e) return e;
+  if (!eps_ok(eps_rel)) return AST_E_UNSUPPORTED;
+  if (workspace_bytes < cov_ws(n, c, m)) return AST_E_SHAPE;
+  return cov_launch(x, mean, cov, n, c, m, eps_rel, (float*)workspace, (hipStream_t)stream);
+}
+
+long long ast_wct_sqrt_workspace_bytes(int b, int c) {
+  if (b <= 0 || c <= 0 || b > 32767) return AST_E_SHAPE;
+  if (c > kMaxC) return AST_E_UNSUPPORTED;
+  return sqrt_ws(b, c);
+}
+
+int ast_wct_sqrt_f32(const float* cov, float* sqrt_or_null, float* isqrt_or_null, int b, int c, int iters,
+                     void* workspace, long long workspace_bytes, void* stream) {
+  if (!cov || !workspace || (!sqrt_or_null && !isqrt_or_null)) return AST_E_NULLPTR;
+  if (b <= 0 || c <= 0 || b > 32767) return AST_E_SHAPE;
+  if (c > kMaxC || iters < 0) return AST_E_UNSUPPORTED;
+  if (workspace_bytes < sqrt_ws(b, c)) return AST_E_SHAPE;
+  if (iters == 0) iters = default_iters(c, 1e-3f);
+  return sqrt_launch(cov, sqrt_or_null, isqrt_or_null, b, c, iters, (unsigned char*)workspace, (hipStream_t)stream);
+}
+
+long long ast_wct_apply_workspace_bytes(int n, int c) {
+  if (n <= 0 || c <= 0 || n > 32767) return AST_E_SHAPE;
+  if (c > kMaxC) return AST_E_UNSUPPORTED;
+  return apply_ws(n, c);
+}
+
+int ast_wct_apply_f32(const float* content, const float* content_mean, const float* style_mean,
+                      const float* style_sqrt, const float* content_isqrt, float* out, int n, int ns, int c,
+                      long long mc, double alpha, void* workspace, long long workspace_bytes, void* stream) {
+  if (!content || !content_mean || !style_mean || !style_sqrt || !content_isqrt || !out || !workspace)
+    return AST_E_NULLPTR;
+  if (ns <= 0 || (ns != n && ns != 1)) return AST_E_SHAPE;
+  const int e = cov_shape(n, c, mc);
+  if (e) return e;
+  if (workspace_bytes < apply_ws(n, c)) return AST_E_SHAPE;
+  return apply_launch(content, content_mean, style_mean, style_sqrt, content_isqrt, out, n, ns, c, mc, (float)alpha,
+                      (float*)workspace, (hipStream_t)stream);
+}
+
+long long ast_wct_workspace_bytes(int n, int ns, int c, long long mc, long long ms) {
+  const int e = pair_shape(n, ns, c, mc, ms);
+  if (e) return e;
+  const int b = n + ns;
+  return al256((int64_t)4 * b * c) + 3 * al256((int64_t)4 * b * c * c) +
+         max3(cov_ws(n, c, mc) > cov_ws(ns, c, ms) ? cov_ws(n, c, mc) : cov_ws(ns, c, ms), sqrt_ws(b, c), apply_ws(n, c));
+}
+
+int ast_wct_f32(const float* content, const float* style, float* out, int n, int ns, int c, int hc, int wc, int hs,
+                int ws, double alpha, float eps_rel, int iters, void* workspace, long long workspace_bytes,
+                void* stream) {
+  if (!content || !style || !out || !workspace) return AST_E_NULLPTR;
+  if (hc <= 0 || wc <= 0 || hs <= 0 || ws <= 0) return AST_E_SHAPE;
+  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws;
+  int e = pair_shape(n, ns, c, mc, ms);
+  if (e) return e;
+  if (!eps_ok(eps_rel) || iters < 0) return AST_E_UNSUPPORTED;
+  if (workspace_bytes < ast_wct_workspace_bytes(n, ns, c, mc, ms)) return AST_E_SHAPE;
+  if (iters == 0) iters = default_iters(c, eps_rel);
+  hipStream_t st = (hipStream_t)stream;
+  // [mean | cov | sqrt | isqrt | scratch], content samples first, then the style's; the scratch is
+  // the covariance partials, then the iteration's buffers, then T: stream order keeps them apart
+  const int b = n + ns;
+  const int64_t cc = (int64_t)c * c, mb = al256((int64_t)4 * b * cc);
+  unsigned char* w = (unsigned char*)workspace;
+  float* mean = (float*)w;
+  float* cov = (float*)(w + al256((int64_t)4 * b * c));
+  float* root = (float*)((unsigned char*)cov + mb);
+  float* iroot = (float*)((unsigned char*)root + mb);
+  unsigned char* scratch = (unsigned char*)iroot + mb;
+  e = cov_launch(content, mean, cov, n, c, mc, eps_rel, (float*)scratch, st);
+  if (e) return e;
+  e = cov_launch(style, mean + (int64_t)n * c, cov + n * cc, ns, c, ms, eps_rel, (float*)scratch, st);
+  if (e) return e;
+  e = sqrt_launch(cov, root, iroot, b, c, iters, scratch, st);
+  if (e) return e;
+  return apply_launch(content, mean, mean + (int64_t)n * c, root + n * cc, iroot, out, n, ns, c, mc, (float)alpha,
+                      (float*)scratch, st);
+}
+
+}  // extern "C"

@@ -35,6 +35,7 @@ region_stats            -- (masked per-region channel statistics)    --
 adain_regions           -- (regional multi-style AdaIN)              --
 efdm                    -- (exact feature distribution matching)     d content = grad (straight-through)
 plane_sort              -- (segmented totalOrder sort of planes)     --
+wct                     -- (whitening and colouring transform)       raises NotImplementedError
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -720,7 +721,29 @@ def _(x):
     return torch.empty_like(x), x.new_empty(x.shape, dtype=torch.int32)
 
 
+# ------------------------------------------------------------------------------------------------
+# Whitening and colouring transform (csrc/wct.hip; inference only)
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::wct", mutates_args=())
+def wct(content: Tensor, style: Tensor, alpha: float, eps_rel: float, iters: int) -> Tensor:
+    """alpha * (T (c - mu_c) + mu_s) + (1 - alpha) * c with T = cov_s^(1/2) cov_c^(-1/2)."""
+    return ops.wct(content, style, alpha=alpha, eps_rel=eps_rel, iters=iters)
+
+
+@register_fake("ast_hip::wct")
+def _(content, style, alpha, eps_rel, iters):
+    return torch.empty_like(content)
+
+
+def _wct_backward(ctx, g):
+    raise NotImplementedError("ast_hip::wct has no backward: the whitening and colouring transform is inference-only")
+
+
+register_autograd("ast_hip::wct", _wct_backward)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions", "efdm", "plane_sort"]
+                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct"]

@@ -61,6 +61,25 @@ class EFDM(nn.Module):
         return ops.efdm(content_map, style_map, alpha=alpha)
 
 
+class WCT(nn.Module):
+    """Whitening and colouring transform (Li et al., NeurIPS 2017) as a drop-in for the AdaIN layer:
+    the content features are whitened with cov_c^(-1/2) and coloured with cov_s^(1/2), so their
+    cross-channel covariance and mean become the style's (ops.wct; the reference has no
+    counterpart). `alpha` fuses the blend alpha * t + (1 - alpha) * c. Inference only: there is no
+    backward. No parameters."""
+
+    def __init__(self, eps_rel: float = ops.WCT_EPS_REL, iters: int = 0):
+        super().__init__()
+        self.eps_rel, self.iters = float(eps_rel), int(iters)
+
+    def forward(self, content_map, style_map, alpha: float = 1.0):
+        if torch.is_grad_enabled() and (content_map.requires_grad or style_map.requires_grad):
+            raise NotImplementedError("WCT is inference-only; run it under torch.no_grad()")
+        if _compiling():
+            return _ops().wct(content_map, style_map, float(alpha), self.eps_rel, self.iters)
+        return ops.wct(content_map, style_map, alpha=alpha, eps_rel=self.eps_rel, iters=self.iters)
+
+
 def calc_mean_std(feat, eps=1e-5):
     """models.py:54-62: per-(n,c) mean and sqrt(unbiased var + eps)."""
     if feat.dim() != 4:
@@ -404,9 +423,11 @@ class AdaINStyleTransfer(nn.Module):
     `transform="efdm"` puts exact feature distribution matching (EFDM) in AdaIN's place, under the
     same attribute name `adain` (what AdaINTrainer calls); the statistics-based methods
     (style_statistics, stylize_with_stats, stylize_regions) then raise NotImplementedError.
+    `transform="wct"` puts the whitening and colouring transform (WCT) there in the same way; it is
+    inference-only (the forward raises NotImplementedError when a gradient is asked for).
     """
 
-    TRANSFORMS = ("adain", "efdm")
+    TRANSFORMS = ("adain", "efdm", "wct")
 
     def __init__(self, canonical: bool = False, enc_seed: int = 1, dec_seed: int = 2, weights="live",
                  transform: str = "adain"):
@@ -415,7 +436,7 @@ class AdaINStyleTransfer(nn.Module):
             raise ValueError(f"transform must be one of {self.TRANSFORMS}, got {transform!r}")
         self.transform = transform
         self.encoder = PretrainedEncoder(content_layers=["relu_9"], weights=weights, seed=enc_seed)
-        self.adain = AdaIN(canonical=canonical) if transform == "adain" else EFDM()
+        self.adain = {"adain": lambda: AdaIN(canonical=canonical), "efdm": EFDM, "wct": WCT}[transform]()
         self.decoder = VGGDecoder(weights=weights, seed=dec_seed)
 
     def _needs_statistics(self, what):

@@ -449,6 +449,84 @@ def plane_sort(x: torch.Tensor, return_index: bool = False, _chunk: int = 0):
     return (vals, index) if return_index else vals
 
 
+# Whitening and colouring transform (csrc/wct.hip): the limits of ast_hip.h
+WCT_MAX_C = 1024
+WCT_EPS_REL = 1e-3
+
+
+def wct_default_iters(c: int, eps_rel: float = WCT_EPS_REL) -> int:
+    """The Newton-Schulz step count that iters=0 selects: ceil(log_2.25(c / eps_rel)) + 5 (the library's
+    own value, so both sides agree): 22 for (512, 1e-3)."""
+    it = int(lib().ast_wct_default_iters(int(c), float(eps_rel)))
+    if it < 0:
+        check(it, f"wct_default_iters(c={c}, eps_rel={eps_rel})")
+    return it
+
+
+def wct_cov(x: torch.Tensor, eps_rel: float = WCT_EPS_REL):
+    """(mean [N, C], cov [N, C, C]) of x [N, C, H, W] (or [N, C, M]): the two-pass centred covariance
+    over each sample's pixels, / (M - 1), plus the ridge eps_rel * max(tr / C, 1e-20) on the diagonal;
+    cov equals its transpose in bits."""
+    x = _dev(x, "x")
+    if x.dim() < 3 or x.numel() == 0:
+        raise HipOpError(f"wct_cov needs a non-empty [N, C, H, W] or [N, C, M] tensor, got {tuple(x.shape)}")
+    n, c = int(x.shape[0]), int(x.shape[1])
+    m = x.numel() // (n * c)
+    L = lib()
+    nbytes = int(L.ast_wct_cov_workspace_bytes(n, c, m))
+    wsb = _ws_bytes(nbytes, "wct_cov workspace", x.device)
+    mean = torch.empty((n, c), device=x.device, dtype=torch.float32)
+    cov = torch.empty((n, c, c), device=x.device, dtype=torch.float32)
+    check(_timed(f"wct_cov {c}ch M={m}", n * c * (c + 1) * m, x.device, lambda: L.ast_wct_cov_f32(
+        ptr(x), ptr(mean), ptr(cov), n, c, m, float(eps_rel), ptr(wsb), nbytes, stream_ptr(x.device))), "wct_cov")
+    return mean, cov
+
+
+def wct_sqrt(cov: torch.Tensor, iters: int = 0, eps_rel: float = WCT_EPS_REL):
+    """(cov^(1/2), cov^(-1/2)) of symmetric positive definite matrices [B, C, C] by `iters` coupled
+    Newton-Schulz steps (0: wct_default_iters(C, eps_rel), eps_rel being the relative ridge that the
+    matrices carry); a fixed count, no convergence test."""
+    cov = _dev(cov, "cov")
+    if cov.dim() != 3 or cov.shape[1] != cov.shape[2] or cov.numel() == 0:
+        raise HipOpError(f"wct_sqrt needs non-empty [B, C, C] matrices, got {tuple(cov.shape)}")
+    b, c = int(cov.shape[0]), int(cov.shape[1])
+    if int(iters) == 0 and c <= WCT_MAX_C:
+        iters = wct_default_iters(c, eps_rel)
+    L = lib()
+    nbytes = int(L.ast_wct_sqrt_workspace_bytes(b, c))
+    wsb = _ws_bytes(nbytes, "wct_sqrt workspace", cov.device)
+    root, iroot = torch.empty_like(cov), torch.empty_like(cov)
+    check(_timed(f"wct_sqrt {b}x{c}", 6 * b * c ** 3 * max(int(iters), 0), cov.device, lambda: L.ast_wct_sqrt_f32(
+        ptr(cov), ptr(root), ptr(iroot), b, c, int(iters), ptr(wsb), nbytes, stream_ptr(cov.device))), "wct_sqrt")
+    return root, iroot
+
+
+def wct(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, eps_rel: float = WCT_EPS_REL,
+        iters: int = 0):
+    """Whitening and colouring transform (Li et al., NeurIPS 2017), a drop-in for adain that matches
+    the cross-channel covariance: out = alpha * (T (c - mu_c) + mu_s) + (1 - alpha) * c with
+    T = cov_s^(1/2) cov_c^(-1/2) (wct_cov, wct_sqrt). content [N, C, Hc, Wc]; style [N, C, Hs, Ws] or
+    [1, C, Hs, Ws] (shared by the batch); C <= 1024, at least 2 pixels per map, eps_rel in [1e-4, 1]."""
+    content = _dev(content, "content_map")
+    style = _dev(style, "style_map")
+    if (content.dim() != 4 or style.dim() != 4 or content.shape[1] != style.shape[1]
+            or style.shape[0] not in (1, content.shape[0]) or content.numel() == 0 or style.numel() == 0):
+        raise HipOpError(f"WCT needs non-empty NCHW maps with equal C and a style batch of N or 1: "
+                         f"{tuple(content.shape)} vs {tuple(style.shape)}")
+    if style.device != content.device:
+        raise HipOpError(f"style_map is on {style.device}, content_map on {content.device}")
+    n, c, hc, wc = (int(s) for s in content.shape)
+    ns, hs, ws = int(style.shape[0]), int(style.shape[2]), int(style.shape[3])
+    L = lib()
+    nbytes = int(L.ast_wct_workspace_bytes(n, ns, c, hc * wc, hs * ws))
+    wsb = _ws_bytes(nbytes, "wct workspace", content.device)
+    out = torch.empty_like(content)
+    check(_timed(f"wct {c}ch {hc}x{wc}", 0, content.device, lambda: L.ast_wct_f32(
+        ptr(content), ptr(style), ptr(out), n, ns, c, hc, wc, hs, ws, float(alpha), float(eps_rel), int(iters),
+        ptr(wsb), nbytes, stream_ptr(content.device))), "wct")
+    return out
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

@@ -205,6 +205,59 @@ int ast_plane_sort_f32(const float* x, float* sorted, int* index_or_null, long l
                        long long m, int chunk, void* workspace, long long workspace_bytes,
                        void* stream);
 
+/* Whitening and colouring transform (WCT, Li et al. NeurIPS 2017; csrc/wct.hip; an extension, no
+ * reference counterpart): the feature transform that matches the cross-channel covariance.
+ * content x [n, c, hc, wc], style s [ns, c, hs, ws] with ns == n, or ns == 1 (one style shared by the
+ * batch); fp32; Mc = hc*wc, Ms = hs*ws, both >= 2. Per sample, with its map viewed as C x M:
+ *   mu    = the per-channel mean;
+ *   Sigma = (X - mu)(X - mu)^T / (M - 1) + eps I, centred in two passes (never E[xx^T] - mu mu^T),
+ *           eps = eps_rel * max(tr / C, 1e-20), tr the trace of the unregularised covariance;
+ *           Sigma equals its transpose bit for bit;
+ *   T     = Sigma_s^(1/2) Sigma_c^(-1/2), the symmetric roots (ZCA whitening, then colouring);
+ *   t     = T (x - mu_c) + mu_s,   out = alpha t + (1 - alpha) x.
+ * A constant content map has tr = 0 exactly (the mean of a constant plane is its value) and gives
+ * out = mu_s at alpha = 1. A non-finite value stays inside its own sample of the batch.
+ * The roots are the coupled Newton-Schulz iteration, which fixes the fp32 behaviour:
+ *   A = Sigma / ||Sigma||_F, Y_0 = A, Z_0 = I;  P_k = 1.5 I - 0.5 Z_k Y_k;
+ *   Y_(k+1) = Y_k P_k, Z_(k+1) = P_k Z_k;  Sigma^(1/2) = Y sqrt(||Sigma||_F), Sigma^(-1/2) = Z / sqrt(||Sigma||_F)
+ * for a fixed count `iters` (never a convergence test on the host). iters = 0 takes the default
+ * ast_wct_default_iters(c, eps_rel) = ceil(log_2.25(c / eps_rel)) + 5 (22 for c = 512, eps_rel =
+ * 1e-3): lambda_min(A) >= eps_rel / c, a small eigenvalue of Z Y grows 2.25x per step, and about five
+ * quadratic steps finish from 0.5. eps_rel must lie in [1e-4, 1] (the default is 1e-3): below that
+ * the fp32 iteration loses a rank-deficient covariance. Every product is an fp32
+ * MFMA; ||.||_F, the trace and the split-K partial tiles of the covariance are summed in a fixed
+ * order. c <= 1024.
+ * Workspaces are device memory, 256-byte aligned, of at least the matching *_workspace_bytes query.
+ * AST_E_SHAPE: a size <= 0, an M below 2, ns outside {1, n}, more than 32767 matrices, a short
+ * workspace. AST_E_UNSUPPORTED: eps_rel outside [1e-4, 1], c > 1024, iters < 0. The queries return
+ * the same negative codes. All checks run before the first launch. */
+int ast_wct_default_iters(int c, float eps_rel);
+
+/* mean [n, c] and cov [n, c, c] (ridge included) of x [n, c, m]. */
+long long ast_wct_cov_workspace_bytes(int n, int c, long long m);
+int ast_wct_cov_f32(const float* x, float* mean, float* cov, int n, int c, long long m, float eps_rel,
+                    void* workspace, long long workspace_bytes, void* stream);
+
+/* Sigma^(1/2) and / or Sigma^(-1/2) [b, c, c] of cov [b, c, c] (either output may be NULL, not both).
+ * iters = 0 is the default count for eps_rel = 1e-3. */
+long long ast_wct_sqrt_workspace_bytes(int b, int c);
+int ast_wct_sqrt_f32(const float* cov, float* sqrt_or_null, float* isqrt_or_null, int b, int c, int iters,
+                     void* workspace, long long workspace_bytes, void* stream);
+
+/* out from the parts: content_mean [n, c], style_mean [ns, c], style_sqrt [ns, c, c],
+ * content_isqrt [n, c, c]; T takes the workspace and t is never stored. */
+long long ast_wct_apply_workspace_bytes(int n, int c);
+int ast_wct_apply_f32(const float* content, const float* content_mean, const float* style_mean,
+                      const float* style_sqrt, const float* content_isqrt, float* out, int n, int ns, int c,
+                      long long mc, double alpha, void* workspace, long long workspace_bytes, void* stream);
+
+/* The whole op: the two covariances, the roots of all n + ns matrices as one batch, the apply. */
+long long ast_wct_workspace_bytes(int n, int ns, int c, long long mc, long long ms);
+int ast_wct_f32(const float* content, const float* style, float* out, int n, int ns, int c,
+                int hc, int wc, int hs, int ws, double alpha, float eps_rel,
+                int iters /* 0 = the default above */, void* workspace, long long workspace_bytes,
+                void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
