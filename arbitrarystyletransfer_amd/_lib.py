@@ -56,6 +56,14 @@ SIGNATURES = {
     "ast_wct_apply_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _d, _p, _ll, _p]),
     "ast_wct_workspace_bytes": (_ll, [_i, _i, _i, _ll, _ll]),
     "ast_wct_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _f, _i, _p, _ll, _p]),
+    "ast_patch_norms_workspace_bytes": (_ll, [_i, _i, _i]),
+    "ast_patch_norms_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_patch_match_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
+    "ast_patch_match_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_patch_match_ex_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_patch_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p]),
+    "ast_style_swap_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
+    "ast_style_swap_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
     "ast_conv3x3_pack_weights_ex_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ast_conv_act_backward_f32": (_i, [_p, _p, _p, _p, _p, _ll, _i, _i, _p]),
     "ast_relu_mask_f32": (_i, [_p, _p, _p, _ll, _p]),

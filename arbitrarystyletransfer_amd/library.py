@@ -36,6 +36,7 @@ adain_regions           -- (regional multi-style AdaIN)              --
 efdm                    -- (exact feature distribution matching)     d content = grad (straight-through)
 plane_sort              -- (segmented totalOrder sort of planes)     --
 wct                     -- (whitening and colouring transform)       raises NotImplementedError
+style_swap              -- (patch-matching style swap)               raises NotImplementedError
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -743,7 +744,29 @@ def _wct_backward(ctx, g):
 register_autograd("ast_hip::wct", _wct_backward)
 
 
+# ------------------------------------------------------------------------------------------------
+# Style swap (csrc/swap.hip; inference only)
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::style_swap", mutates_args=())
+def style_swap(content: Tensor, style: Tensor, alpha: float, normalize: bool) -> Tensor:
+    """Every 3x3 content patch replaced by its best-matching style patch, overlaps averaged (+ alpha blend)."""
+    return ops.style_swap(content, style, alpha=alpha, normalize=normalize)
+
+
+@register_fake("ast_hip::style_swap")
+def _(content, style, alpha, normalize):
+    return torch.empty_like(content)
+
+
+def _style_swap_backward(ctx, g):
+    raise NotImplementedError("ast_hip::style_swap has no backward: style swap is inference-only")
+
+
+register_autograd("ast_hip::style_swap", _style_swap_backward)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct"]
+                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "style_swap"]

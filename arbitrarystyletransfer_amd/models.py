@@ -80,6 +80,26 @@ class WCT(nn.Module):
         return ops.wct(content_map, style_map, alpha=alpha, eps_rel=self.eps_rel, iters=self.iters)
 
 
+class StyleSwap(nn.Module):
+    """Style swap (Chen & Schmidt 2016): every 3x3 patch of the content map is replaced by the most
+    similar 3x3 patch of the style map and the overlaps are averaged, so the result is made of the
+    style's own local structure (ops.style_swap; the reference has no counterpart).
+    `normalize=True` matches on the instance-normalised maps and reconstructs from the raw style
+    features (the style decorator of Avatar-Net). `alpha` fuses the blend alpha * t + (1 - alpha) * c.
+    Inference only: there is no backward. No parameters."""
+
+    def __init__(self, normalize: bool = False):
+        super().__init__()
+        self.normalize = bool(normalize)
+
+    def forward(self, content_map, style_map, alpha: float = 1.0):
+        if torch.is_grad_enabled() and (content_map.requires_grad or style_map.requires_grad):
+            raise NotImplementedError("StyleSwap is inference-only; run it under torch.no_grad()")
+        if _compiling():
+            return _ops().style_swap(content_map, style_map, float(alpha), self.normalize)
+        return ops.style_swap(content_map, style_map, alpha=alpha, normalize=self.normalize)
+
+
 def calc_mean_std(feat, eps=1e-5):
     """models.py:54-62: per-(n,c) mean and sqrt(unbiased var + eps)."""
     if feat.dim() != 4:
@@ -425,6 +445,8 @@ class AdaINStyleTransfer(nn.Module):
     (style_statistics, stylize_with_stats, stylize_regions) then raise NotImplementedError.
     `transform="wct"` puts the whitening and colouring transform (WCT) there in the same way; it is
     inference-only (the forward raises NotImplementedError when a gradient is asked for).
+    `stylize_swap` stylises by style swap (patch matching on the relu4_1 maps) with the same
+    encoder and decoder, whatever the transform.
     """
 
     TRANSFORMS = ("adain", "efdm", "wct")
@@ -461,6 +483,26 @@ class AdaINStyleTransfer(nn.Module):
             self._check_preserve_color(content_img, style_img)
         f_c, f_s = self.encode_pair(content_img, style_img)
         t = self.adain(f_c, f_s, alpha=alpha)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
+
+    def stylize_swap(self, content_img, style_img, alpha: float = 1.0, normalize: bool = False,
+                     preserve_color: bool = False):
+        """Stylise by style swap (StyleSwap on the relu4_1 maps) instead of the model's feature
+        transform: the same encoder, decoder and weights, whatever `transform` the model was built
+        with. The two images may differ in size (each side at least 24 pixels: a 3x3 relu4_1 map);
+        style_img is [N, 3, Hs, Ws] or [1, 3, Hs, Ws]. Inference only; normalize as StyleSwap,
+        preserve_color as in forward."""
+        if torch.is_grad_enabled() and (content_img.requires_grad or style_img.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("stylize_swap is inference-only; run it under torch.no_grad()")
+        f_c, f_s = self.encode_pair(content_img, style_img)
+        if _compiling():
+            t = _ops().style_swap(f_c, f_s, float(alpha), bool(normalize))
+        else:
+            t = ops.style_swap(f_c, f_s, alpha=alpha, normalize=bool(normalize))
         out = self.decoder(t)
         if preserve_color:
             return _luma_transfer(out, content_img)

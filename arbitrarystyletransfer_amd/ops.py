@@ -527,6 +527,84 @@ def wct(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, eps_rel:
     return out
 
 
+# Style swap (csrc/swap.hip): the limits of ast_hip.h
+SWAP_MAX_C = 1024
+
+
+def _swap_pair(a: torch.Tensor, b: torch.Tensor, na: str, nb: str, what: str):
+    """Two fp32 device NCHW maps with equal C, sides of at least 3 and b's batch equal to a's or 1:
+    (a, b, n, ns, c, ha, wa, hb, wb)."""
+    a, b = _dev(a, na), _dev(b, nb)
+    if (a.dim() != 4 or b.dim() != 4 or a.shape[1] != b.shape[1] or b.shape[0] not in (1, a.shape[0])
+            or a.numel() == 0 or b.numel() == 0 or min(a.shape[2:]) < 3 or min(b.shape[2:]) < 3):
+        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C, sides of at least 3 and a style batch of N "
+                         f"or 1: {na} {tuple(a.shape)} vs {nb} {tuple(b.shape)}")
+    if a.device != b.device:
+        raise HipOpError(f"{nb} is on {b.device}, {na} on {a.device}")
+    n, c, ha, wa = (int(s) for s in a.shape)
+    return a, b, n, int(b.shape[0]), c, ha, wa, int(b.shape[2]), int(b.shape[3])
+
+
+def patch_match(content_key: torch.Tensor, style_key: torch.Tensor, return_score: bool = False, _splits: int = 0):
+    """For every 3x3 patch of content_key [N, C, H, W], the index jy * (Ws - 2) + jx of the 3x3 patch of
+    style_key [N or 1, C, Hs, Ws] with the largest <content patch, style patch> / ||style patch||
+    (the lowest index on equal scores; a zero style patch scores 0; a NaN never wins): int32
+    [N, H - 2, W - 2], and the winning score with return_score. The scores are never stored.
+    _splits forces the number of workgroups that share the style patches (0: the library's choice)."""
+    ck, sk, n, ns, c, hc, wc, hs, ws = _swap_pair(content_key, style_key, "content_key", "style_key", "patch_match")
+    L, dev, st = lib(), ck.device, stream_ptr(ck.device)
+    nb = int(L.ast_patch_norms_workspace_bytes(ns, hs, ws))
+    wsn = _ws_bytes(nb, "patch_norms workspace", dev)
+    inv = torch.empty((ns, hs - 2, ws - 2), device=dev, dtype=torch.float32)
+    check(L.ast_patch_norms_f32(ptr(sk), ptr(inv), ns, c, hs, ws, ptr(wsn), nb, st), "patch_norms")
+    mb = int(L.ast_patch_match_workspace_bytes(n, ns, hc, wc, hs, ws, int(_splits)))
+    wsm = _ws_bytes(mb, "patch_match workspace", dev)
+    index = torch.empty((n, hc - 2, wc - 2), device=dev, dtype=torch.int32)
+    score = torch.empty((n, hc - 2, wc - 2), device=dev, dtype=torch.float32) if return_score else None
+    flops = 2 * n * (hc - 2) * (wc - 2) * (hs - 2) * (ws - 2) * 9 * c
+    check(_timed(f"patch_match {c}ch {hc}x{wc} vs {hs}x{ws}", flops, dev, lambda: L.ast_patch_match_ex_f32(
+        ptr(ck), ptr(sk), ptr(inv), ptr(index), ptr(score), n, ns, c, hc, wc, hs, ws, int(_splits), ptr(wsm), mb, st)),
+        "patch_match")
+    return (index, score) if return_score else index
+
+
+def patch_gather(style_value: torch.Tensor, index: torch.Tensor, content: torch.Tensor, alpha: float = 1.0):
+    """The reconstruction of style swap: out[y, x] = (1 - alpha) content[y, x] + alpha * the mean, over the
+    up-to-nine content patches covering (y, x), of the style_value pixel that the patch's match
+    (index [N, H - 2, W - 2] int32, as patch_match returns) puts there. One launch."""
+    c_, sv, n, ns, c, hc, wc, hs, ws = _swap_pair(content, style_value, "content_map", "style_value", "patch_gather")
+    if (not isinstance(index, torch.Tensor) or index.device != c_.device or index.dtype != torch.int32
+            or tuple(index.shape) != (n, hc - 2, wc - 2)):
+        raise HipOpError(f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
+    index = index.contiguous()
+    out = torch.empty_like(c_)
+    check(_timed(f"patch_gather {c}ch {hc}x{wc}", -4 * 11 * c_.numel(), c_.device, lambda: lib().ast_patch_gather_f32(
+        ptr(sv), ptr(index), ptr(c_), ptr(out), n, ns, c, hc, wc, hs, ws, float(alpha), stream_ptr(c_.device))),
+        "patch_gather")
+    return out
+
+
+def style_swap(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, normalize: bool = False,
+               return_index: bool = False):
+    """Style swap (Chen & Schmidt 2016): every 3x3 patch of content [N, C, H, W] is replaced by the most
+    similar 3x3 patch of style [N or 1, C, Hs, Ws] (patch_match), the overlaps are averaged and
+    blended with the content by alpha (patch_gather). normalize=True matches on the per-channel
+    instance-normalised maps (mean_variance_norm) and reconstructs from the raw style features, the
+    style decorator of Avatar-Net. return_index adds the int32 match [N, H - 2, W - 2]."""
+    c_, s_, n, ns, c, hc, wc, hs, ws = _swap_pair(content, style, "content_map", "style_map", "style_swap")
+    ck, sk = (mean_variance_norm(c_), mean_variance_norm(s_)) if normalize else (c_, s_)
+    L = lib()
+    nbytes = int(L.ast_style_swap_workspace_bytes(n, ns, hc, wc, hs, ws))
+    wsb = _ws_bytes(nbytes, "style_swap workspace", c_.device)
+    out = torch.empty_like(c_)
+    index = torch.empty((n, hc - 2, wc - 2), device=c_.device, dtype=torch.int32) if return_index else None
+    flops = 2 * n * (hc - 2) * (wc - 2) * (hs - 2) * (ws - 2) * 9 * c
+    check(_timed(f"style_swap {c}ch {hc}x{wc} vs {hs}x{ws}", flops, c_.device, lambda: L.ast_style_swap_f32(
+        ptr(ck), ptr(sk), ptr(s_), ptr(c_), ptr(out), ptr(index), None, n, ns, c, hc, wc, hs, ws, float(alpha),
+        ptr(wsb), nbytes, stream_ptr(c_.device))), "style_swap")
+    return (out, index) if return_index else out
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

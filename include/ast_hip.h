@@ -258,6 +258,69 @@ int ast_wct_f32(const float* content, const float* style, float* out, int n, int
                 int iters /* 0 = the default above */, void* workspace, long long workspace_bytes,
                 void* stream);
 
+/* Style swap (Chen & Schmidt 2016; the style decorator of Avatar-Net, Sheng et al. CVPR 2018, when the
+ * keys are normalised features; csrc/swap.hip; an extension, no reference counterpart): every 3x3
+ * patch of the content map is replaced by the most similar patch of the style map and the overlaps
+ * are averaged.
+ * Inputs, all fp32 dense NCHW: content key ck [n, c, hc, wc], style key sk and style value sv
+ * [ns, c, hs, ws] with ns == n, or ns == 1 (one style shared by the batch), content x [n, c, hc, wc].
+ * Every side is at least 3, a map has at most 2^24 pixels, n <= 65535, c in 1..1024.
+ * Patches: content patch i = y (wc - 2) + x exists for 0 <= y <= hc - 3, 0 <= x <= wc - 3, style patch
+ * j = jy (ws - 2) + jx for 0 <= jy <= hs - 3, 0 <= jx <= ws - 3; a patch is the c x 3 x 3 block whose
+ * top-left corner is at that position.
+ * Match: score(i, j) = <ck patch i, sk patch j> / ||sk patch j||_2; a style patch of zero norm scores
+ * exactly 0; index(i) = the j of maximal score, the lowest j on exactly equal scores; a NaN score
+ * never wins. A score replaces the running pair (-inf, 0) only when strictly greater, so a content
+ * patch for which nothing wins returns index 0 (and score -inf). The content patch's own norm does
+ * not enter. index [n, hc - 2, wc - 2] int32 and the winning score [same shape] are outputs.
+ * A score is one fp32 fma chain over (channel, tap) in a fixed order times the style patch's inverse
+ * norm: it depends on the values of the two patches only, not on where the style patch sits, which
+ * tile it falls in or how the style patches were split across workgroups.
+ * Reconstruct: with (jy, jx) = index(y - dy, x - dx),
+ *   out[n, ch, y, x] = (1 - alpha) x[n, ch, y, x] + alpha (1 / cnt(y, x)) sum sv[n', ch, jy + dy, jx + dx]
+ * over the (dy, dx) in {0, 1, 2}^2 whose content patch (y - dy, x - dx) exists, in ascending (dy, dx)
+ * order; cnt, 1..9, is the number of such terms. An index outside 0 .. (hs - 2)(ws - 2) - 1 given to
+ * ast_patch_gather_f32 is clamped into that range.
+ * Three stages and their composition, ast_style_swap_f32 (bit for bit). Workspaces are device
+ * memory, 256-byte aligned, of at least the matching *_workspace_bytes query. No atomics, no host
+ * synchronisation; a non-finite value stays inside its own sample of the batch.
+ * AST_E_NULLPTR: a null pointer. AST_E_SHAPE: a side below 3, a size <= 0 or over the limits above, ns
+ * outside {1, n}, a short workspace. AST_E_UNSUPPORTED: c > 1024, splits < 0. The queries return the
+ * same negative codes. All checks run before the first launch. */
+
+/* inv_norm [ns, (hs - 2)(ws - 2)] = 1 / ||sk patch j||_2, 0 for a zero (or non-finite) norm: the squared
+ * norm of every pixel over the channels, a 3x3 box sum, a reciprocal square root, in the same order
+ * at every position, so two equal style patches have equal inverse norms in bits. */
+long long ast_patch_norms_workspace_bytes(int ns, int hs, int ws);
+int ast_patch_norms_f32(const float* style_key, float* inv_norm, int ns, int c, int hs, int ws,
+                        void* workspace, long long workspace_bytes, void* stream);
+
+/* index (and score, when given) from the keys and the inverse norms. The style patches are split
+ * across workgroups when the content tiles alone cannot fill the chip; the _ex form takes the split
+ * count: 0 = the library's choice (what the plain entry passes), else that many (clamped to the
+ * number of 64-patch style tiles and to 64). The result does not depend on it, bit for bit. The
+ * query takes the same splits. */
+long long ast_patch_match_workspace_bytes(int n, int ns, int hc, int wc, int hs, int ws, int splits);
+int ast_patch_match_f32(const float* content_key, const float* style_key, const float* inv_norm,
+                        int* index, float* score_or_null, int n, int ns, int c, int hc, int wc,
+                        int hs, int ws, void* workspace, long long workspace_bytes, void* stream);
+int ast_patch_match_ex_f32(const float* content_key, const float* style_key, const float* inv_norm,
+                           int* index, float* score_or_null, int n, int ns, int c, int hc, int wc,
+                           int hs, int ws, int splits, void* workspace, long long workspace_bytes,
+                           void* stream);
+
+/* out from the style value, the indices and the content (the alpha blend fused); one launch. */
+int ast_patch_gather_f32(const float* style_value, const int* index, const float* content, float* out,
+                         int n, int ns, int c, int hc, int wc, int hs, int ws, double alpha,
+                         void* stream);
+
+/* The whole op: norms of style_key, match, gather. index and score are written when given. */
+long long ast_style_swap_workspace_bytes(int n, int ns, int hc, int wc, int hs, int ws);
+int ast_style_swap_f32(const float* content_key, const float* style_key, const float* style_value,
+                       const float* content, float* out, int* index_or_null, float* score_or_null,
+                       int n, int ns, int c, int hc, int wc, int hs, int ws, double alpha,
+                       void* workspace, long long workspace_bytes, void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
