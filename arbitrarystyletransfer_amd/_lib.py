@@ -64,6 +64,11 @@ SIGNATURES = {
     "ast_patch_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ast_style_swap_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "ast_style_swap_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
+    "ast_patch_match_guided_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
+    "ast_patch_match_guided_ex_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_patch_gather_guided_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p]),
+    "ast_style_swap_guided_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
+    "ast_style_swap_guided_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
     "ast_conv3x3_pack_weights_ex_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ast_conv_act_backward_f32": (_i, [_p, _p, _p, _p, _p, _ll, _i, _i, _p]),
     "ast_relu_mask_f32": (_i, [_p, _p, _p, _ll, _p]),

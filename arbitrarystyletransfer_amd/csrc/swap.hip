@@ -33,6 +33,14 @@
 //                  stored.
 //   gather         the overlap average with the alpha blend fused, one launch: a thread decodes the
 //                  up-to-nine source positions of its pixel once and walks the channels.
+// Guided style swap (semantic patch transfer) is the same three stages over a bank of S styles shared
+// by the batch, with one uint8 class per content patch and per style patch: a content patch is matched
+// only against the style patches of its own class (a class >= AST_SWAP_MAX_CLASSES takes no part), the
+// index is global over the bank, j = s Ns + local, and -1 where nothing is admissible. The match is the
+// guided instantiation of the same kernel, scores bit-equal to the unguided one's; a pre-kernel writes
+// one 64-bit class-presence mask per 64-patch tile and a workgroup visits only the bank tiles whose
+// mask meets its content tile's. The gather skips negative indices and copies the content where no
+// covering patch has a match. ast_style_swap_guided_f32 is norms, masks, match, gather.
 // No atomics, no host synchronisation, no allocation: every sample is indexed by a grid dimension, so
 // a non-finite value stays inside its own sample.
 #include <hip/hip_runtime.h>
@@ -149,22 +157,71 @@ __device__ __forceinline__ void fold(float& v, int& ix, float ov, int oi) {
   }
 }
 
-// grid (content tiles, splits, samples). Writes (score, index) of content patch i of sample b and
-// split s at [(b * splits + s) * M + i]: the outputs themselves when splits == 1. NP = 2 (runs of up to
-// 128 pixels) covers every map at least 5 wide on both sides; NP = 3 the narrower ones.
-template <int NP>
+// What the guided match reads beside the unguided one's inputs: one class
+// per content patch [n, M] and per style patch of the bank [S, Ns], and the class-presence masks of
+// the 64-patch tiles, bit k = "some patch of the tile has class k", content [n, content tiles] and
+// bank [S * tiles per style].
+struct Guide {
+  const uint8_t* cc;
+  const uint8_t* sc;
+  const unsigned long long* cmask;
+  const unsigned long long* bmask;
+  int flags;
+};
+
+// The guided instantiation of the match kernel has one more argument, a Guide; the unguided one none,
+// so its signature is what it was.
+template <class... G>
+__device__ __forceinline__ Guide guide_of(G... g) {
+  if constexpr (sizeof...(G) == 1)
+    return (g, ...);
+  else
+    return Guide{};
+}
+
+// A 64-bit value that every lane holds equal, moved to scalar registers: what a branch around a
+// barrier may depend on.
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// The first bank tile in [t, end) whose classes meet the content tile's `cm` -- every tile when `all`
+// (AST_SWAP_NO_SKIP) --, or `end`. Workgroup-uniform by construction: t, end and cm are scalars of the
+// workgroup (block indices, kernel arguments and readfirstlane results), every thread reads the same
+// mask words in the same order, and the result passes through readfirstlane again.
+__device__ __forceinline__ int next_visited(const unsigned long long* __restrict__ bmask, unsigned long long cm, int t,
+                                            int end, bool all) {
+  if (!all)
+    while (t < end && !(uniform64(bmask[t]) & cm)) ++t;
+  return __builtin_amdgcn_readfirstlane(min(t, end));
+}
+
+// The match of one workgroup: grid (content tiles, splits, samples). Writes (score, index) of content
+// patch i of sample b and split s at [(b * splits + s) * M + i]: the outputs themselves when
+// splits == 1. NP = 2 (runs of up to 128 pixels) covers every map at least 5 wide on both sides; NP = 3
+// the narrower ones. GUIDED: the style maps are a bank of `style_batch` styles shared by the batch,
+// bank tile t = (style t / tiles per style, local tile t % tiles per style) so that no tile straddles
+// two styles, the index is the global s Ns + local one, a style patch is admitted for an accumulator
+// row only where the row's content class equals its own, a bank tile is visited only if its class mask
+// meets the content tile's, and a patch without a winner returns index -1.
+template <int NP, class... G>
 __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict__ ck, const float* __restrict__ sk,
                                                        const float* __restrict__ inv, float* __restrict__ oscore,
                                                        int* __restrict__ oindex, int C, int H, int W, int Hs, int Ws,
-                                                       int style_batch, int tiles_per_split) {
+                                                       int style_batch, int tiles_per_split, G... guide) {
+  constexpr bool GUIDED = sizeof...(G) == 1;
+  const Guide g = guide_of(guide...);
   constexpr int SEG = 64 * NP;  // floats per run
   __shared__ float As[ROWS * SEG];
   __shared__ float Bs[ROWS * SEG];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave & 1, wn = wave >> 1;
   const int pw = W - 2, M = (H - 2) * pw, pws = Ws - 2, N = (Hs - 2) * pws, hw = H * W, hws = Hs * Ws;
-  const int b = blockIdx.z, bs = style_batch == 1 ? 0 : b, split = blockIdx.y;
-  const int m0 = blockIdx.x * MT, ntiles = (N + MT - 1) / MT;
+  const int b = blockIdx.z, bs = GUIDED ? 0 : style_batch == 1 ? 0 : b, split = blockIdx.y;
+  const int tps = (N + MT - 1) / MT;  // 64-patch tiles of one style map
+  const int m0 = blockIdx.x * MT, ntiles = GUIDED ? style_batch * tps : tps;
   const int jt_beg = split * tiles_per_split, jt_end = min(jt_beg + tiles_per_split, ntiles);
   const float* Ab = ck + (int64_t)b * C * hw;
   const float* Bb = sk + (int64_t)bs * C * hws;
@@ -179,32 +236,69 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     best[i] = -INFINITY;
-    bidx[i] = 0;
+    bidx[i] = GUIDED ? -1 : 0;
+  }
+
+  // GUIDED: the classes of the lane's 16 accumulator rows, four to a register (rows 4 q .. 4 q + 3 are
+  // consecutive content patches), 0xff for "takes no part"; the content tile's class mask; the first
+  // tile to visit and the style it lies in.
+  unsigned ccls[4] = {0u, 0u, 0u, 0u};
+  unsigned long long cm = 0;
+  bool all = true;
+  int jt0 = jt_beg, sty = 0;
+  if constexpr (GUIDED) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int gi = m0 + wm * 32 + 8 * q + 4 * h + k;
+        const unsigned v = gi < M ? g.cc[(int64_t)b * M + gi] : 0xffu;
+        ccls[q] |= (v < AST_SWAP_MAX_CLASSES ? v : 0xffu) << (8 * k);
+      }
+    cm = uniform64(g.cmask[(int64_t)b * gridDim.x + blockIdx.x]);
+    all = (g.flags & AST_SWAP_NO_SKIP) != 0;
+    jt0 = next_visited(g.bmask, cm, jt_beg, jt_end, all);
+    sty = jt0 / tps;
+    Bb += (int64_t)sty * C * hws;
   }
 
   float ra[RT][NP], rb[RT][NP];
-  int pb0 = pix_of(jt_beg * MT, pws), pn0 = pb0;  // and of the style tile's, this one and the next
+  int pb0 = pix_of((jt0 - sty * tps) * MT, pws), pn0 = pb0;  // and of the style tile's, this one and the next
   const Plan pa = stage_plan(hw, W, pa0, wave, lane);
   Plan pb = stage_plan(hws, Ws, pb0, wave, lane);
-  if (jt_beg < jt_end) {
+  if (jt0 < jt_end) {
     stage_load<NP>(ra, Ab, C, hw, pa);
     stage_load<NP>(rb, Bb, C, hws, pb);
   }
-  for (int jt = jt_beg; jt < jt_end; ++jt) {
-    const int j = jt * MT + wn * 32 + r;
-    const bool jvalid = j < N;
-    const float* Br = Bs + h * 3 * SEG + (jvalid ? pix_of(j, pws) - pb0 : 0);
+  // Every branch below that encloses a barrier depends on jt, jn and jt_end alone, and these are
+  // workgroup-uniform: jt_end comes from block indices and kernel arguments, jt and jn from
+  // next_visited (see there). So all 256 threads visit the same tiles and meet at every barrier.
+  // GUIDED: jn is the tile visited after jt (jt_end: none); Bb, sty and pb describe tile jt at the top
+  // of the body and are moved on to jn at its last chunk. Unguided, the next tile is jt + 1.
+  for (int jt = GUIDED ? jt0 : jt_beg, jn = 0; jt < jt_end; GUIDED ? (jt = jn) : ++jt) {
+    if constexpr (GUIDED) jn = next_visited(g.bmask, cm, jt + 1, jt_end, all);
+    const int st = sty, jl = (jt - st * tps) * MT + wn * 32 + r;  // this tile's style, the lane's patch in it
+    const int j = st * N + jl;
+    const bool jvalid = jl < N;
+    const float* Br = Bs + h * 3 * SEG + (jvalid ? pix_of(jl, pws) - pb0 : 0);
     f32x16 acc = (f32x16){0.f};
     for (int c0 = 0; c0 < C; c0 += KC) {
       stage_store<NP>(ra, As, wave, lane);
       stage_store<NP>(rb, Bs, wave, lane);
       __syncthreads();
-      // the next chunk -- the next style tile's first one after this tile's last -- is in flight
+      // the next chunk -- the next visited style tile's first one after this tile's last -- is in flight
       // while this one is multiplied; the workgroup's last step loads a chunk again that nobody uses
       const bool wrap = c0 + KC >= C;
       const int nc0 = wrap ? 0 : c0 + KC;
-      if (wrap && jt + 1 < jt_end) {
-        pn0 = pix_of((jt + 1) * MT, pws);
+      if (wrap && (GUIDED ? jn : jt + 1) < jt_end) {
+        if constexpr (GUIDED) {
+          const int sn = jn / tps;
+          Bb += (int64_t)(sn - sty) * C * hws;
+          sty = sn;
+          pn0 = pix_of((jn - sn * tps) * MT, pws);
+        } else {
+          pn0 = pix_of((jt + 1) * MT, pws);
+        }
         pb = stage_plan(hws, Ws, pn0, wave, lane);
       }
       stage_load<NP>(ra, Ab + (int64_t)nc0 * hw, C - nc0, hw, pa);
@@ -224,12 +318,27 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
       __syncthreads();
     }
     const float iv = jvalid ? invb[j] : 0.f;
+    if constexpr (GUIDED) {
+      // the lane's column is one style patch with one class, loaded beside its inverse norm; 0xfe
+      // ("never a candidate") equals no content class
+      const unsigned v = jvalid ? g.sc[j] : 0xfeu;
+      const unsigned scls = v < AST_SWAP_MAX_CLASSES ? v : 0xfeu;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float s = acc[i] * iv;
-      if (jvalid && s > best[i]) {  // j grows from tile to tile: the lowest j of equal scores stays
-        best[i] = s;
-        bidx[i] = j;
+      for (int i = 0; i < 16; ++i) {
+        const float s = acc[i] * iv;
+        if (((ccls[i >> 2] >> (8 * (i & 3))) & 0xffu) == scls && s > best[i]) {
+          best[i] = s;
+          bidx[i] = j;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float s = acc[i] * iv;
+        if (jvalid && s > best[i]) {  // j grows from tile to tile: the lowest j of equal scores stays
+          best[i] = s;
+          bidx[i] = j;
+        }
       }
     }
     pb0 = pn0;
@@ -275,15 +384,33 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
   }
 }
 
+// grid (tiles, maps), one wave per 64-patch tile: mask[map, tile] = OR over the tile's patches of
+// 1 << class, a class >= AST_SWAP_MAX_CLASSES or a patch past the map giving no bit; an OR-reduction
+// across the wave's lanes.
+__global__ __launch_bounds__(64) void swap_class_mask_kernel(const uint8_t* __restrict__ cls,
+                                                            unsigned long long* __restrict__ mask, int P) {
+  const int lane = threadIdx.x, i = blockIdx.x * MT + lane;
+  const unsigned v = i < P ? cls[(int64_t)blockIdx.y * P + i] : 0xffu;
+  unsigned lo = v < 32 ? 1u << v : 0u, hi = (v >= 32 && v < AST_SWAP_MAX_CLASSES) ? 1u << (v - 32) : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo |= (unsigned)__shfl_xor((int)lo, o, 64);
+    hi |= (unsigned)__shfl_xor((int)hi, o, 64);
+  }
+  if (lane == 0) mask[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((unsigned long long)hi << 32) | lo;
+}
+
 // grid (patches / 256, samples): the splits of a content patch in split order; a later split holds
-// higher j only, so strictly greater keeps the lowest j of equal scores.
+// higher j only, so strictly greater keeps the lowest j of equal scores. NONE is the index of a patch
+// for which no split has a winner: 0, or -1 for the guided match.
+template <int NONE>
 __global__ __launch_bounds__(kT) void swap_merge_kernel(const float* __restrict__ pscore, const int* __restrict__ pindex,
                                                        float* __restrict__ score, int* __restrict__ index, int M,
                                                        int splits) {
   const int i = blockIdx.x * kT + threadIdx.x, b = blockIdx.y;
   if (i >= M) return;
   float v = -INFINITY;
-  int ix = 0;
+  int ix = NONE;
   for (int s = 0; s < splits; ++s) {
     const int64_t o = ((int64_t)b * splits + s) * M + i;
     const float ov = pscore[o];
@@ -337,6 +464,53 @@ __global__ __launch_bounds__(kT) void swap_gather_kernel(const float* __restrict
   }
 }
 
+// The guided gather, same grid: the index is global over a bank of `styles` maps, j = s Ns + local; a
+// negative index is "no match" and adds no term; a pixel none of whose covering patches has a match
+// is a copy of the content.
+__global__ __launch_bounds__(kT) void swap_gather_guided_kernel(const float* __restrict__ sv,
+                                                               const int* __restrict__ index,
+                                                               const float* __restrict__ content,
+                                                               float* __restrict__ out, int C, int H, int W, int Hs,
+                                                               int Ws, int styles, float alpha) {
+  const int hw = H * W, hws = Hs * Ws, pw = W - 2, pws = Ws - 2, N = (Hs - 2) * pws;
+  const int p = blockIdx.x * kT + threadIdx.x, b = blockIdx.z;
+  if (p >= hw) return;
+  const int y = p / W, x = p - y * W;
+  const int* idx = index + (int64_t)b * (H - 2) * pw;
+  const int last = styles * N - 1;  // < 2^31: checked on the host
+  int64_t src[9];                   // the source pixel's offset in its style's channel 0, or -1
+  int cnt = 0;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int py = y - dy, px = x - dx;
+      int64_t s = -1;
+      if (py >= 0 && py <= H - 3 && px >= 0 && px <= W - 3) {
+        const int j = min(idx[py * pw + px], last);  // a caller's index past the bank is clamped
+        if (j >= 0) {
+          const int st = j / N;
+          s = (int64_t)st * C * hws + pix_of(j - st * N, pws) + dy * Ws + dx;
+          ++cnt;
+        }
+      }
+      src[dy * 3 + dx] = s;
+    }
+  const float rc = 1.0f / (float)cnt, beta = 1.f - alpha;
+  const int c_beg = blockIdx.y * GC, c_end = min(c_beg + GC, C);
+  const int64_t ob = (int64_t)b * C * hw + p;
+  for (int c = c_beg; c < c_end; ++c) {
+    const float* Vc = sv + (int64_t)c * hws;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      if (src[k] >= 0) s += Vc[src[k]];
+    const int64_t o = ob + (int64_t)c * hw;
+    const float x0 = content[o];
+    out[o] = cnt ? beta * x0 + alpha * (s * rc) : x0;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side: argument checks, workspace layouts, launch sequences
 // ------------------------------------------------------------------------------------------------
@@ -362,9 +536,7 @@ inline int chan_shape(int c) { return c <= 0 ? AST_E_SHAPE : c > kMaxC ? AST_E_U
 // Splits of the style tiles: as asked (clamped to the tiles), or, for 0, as many as bring the grid to
 // kTargetWGs workgroups -- about 16 per CU: three are resident per CU and short ones even out the tail
 // (measured at C = 512, 64 x 64: 61 splits at n = 1, 9 at n = 8) --; then rounded so that no split is empty.
-inline int match_splits(int n, int hc, int wc, int hs, int ws, int want, int* tiles_per_split) {
-  const int ntiles = tiles_of(patches(hs, ws));
-  const int64_t wgs = (int64_t)n * tiles_of(patches(hc, wc));
+inline int split_tiles(int64_t wgs, int ntiles, int want, int* tiles_per_split) {
   int64_t s = want > 0 ? want : (kTargetWGs + wgs - 1) / wgs;
   if (s > kMaxSplits) s = kMaxSplits;
   if (s > ntiles) s = ntiles;
@@ -372,6 +544,10 @@ inline int match_splits(int n, int hc, int wc, int hs, int ws, int want, int* ti
   const int tps = (int)((ntiles + s - 1) / s);
   if (tiles_per_split) *tiles_per_split = tps;
   return (ntiles + tps - 1) / tps;
+}
+
+inline int match_splits(int n, int hc, int wc, int hs, int ws, int want, int* tiles_per_split) {
+  return split_tiles((int64_t)n * tiles_of(patches(hc, wc)), tiles_of(patches(hs, ws)), want, tiles_per_split);
 }
 
 inline int64_t norms_ws(int ns, int hs, int ws) { return al256((int64_t)4 * ns * hs * ws); }
@@ -407,7 +583,7 @@ int match_launch(const float* ck, const float* sk, const float* inv, int* index,
     float* ps = (float*)(wsp + one);
     int* pi = (int*)(wsp + one + al256((int64_t)4 * n * splits * m));
     hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, ps, pi, c, hc, wc, hs, ws, ns, tps);
-    hipLaunchKernelGGL(swap_merge_kernel, dim3((m + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)ps, (const int*)pi,
+    hipLaunchKernelGGL(swap_merge_kernel<0>, dim3((m + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)ps, (const int*)pi,
                        score, index, m, splits);
   }
   return (int)hipGetLastError();
@@ -417,6 +593,71 @@ int gather_launch(const float* sv, const int* index, const float* content, float
                   int wc, int hs, int ws, float alpha, hipStream_t st) {
   hipLaunchKernelGGL(swap_gather_kernel, dim3((hc * wc + kT - 1) / kT, (c + GC - 1) / GC, n), dim3(kT), 0, st, sv, index,
                      content, out, c, hc, wc, hs, ws, ns, alpha);
+  return (int)hipGetLastError();
+}
+
+// ---- guided: a bank of S styles shared by the batch, one class per patch ------------------------------
+
+// AST_OK, or the code that rejects n content maps hc x wc against a bank of S maps hs x ws
+inline int bank_shape(int n, int S, int hc, int wc, int hs, int ws) {
+  if (n <= 0 || S <= 0) return AST_E_SHAPE;
+  int e = map_shape(n, hc, wc);
+  if (!e) e = map_shape(S, hs, ws);
+  if (!e && (int64_t)S * patches(hs, ws) > INT32_MAX) e = AST_E_SHAPE;  // the global style patch index is an int32
+  return e;
+}
+
+inline int bank_tiles(int S, int hs, int ws) { return S * tiles_of(patches(hs, ws)); }
+
+// Splits of the bank tiles, chosen as the unguided match chooses them: equal runs of bank tiles,
+// whatever the classes are (the count must not depend on device data). Under skipping the runs do
+// unequal work; the grid is many workgroups per CU, which evens that out.
+inline int guided_splits(int n, int S, int hc, int wc, int hs, int ws, int want, int* tiles_per_split) {
+  return split_tiles((int64_t)n * tiles_of(patches(hc, wc)), bank_tiles(S, hs, ws), want, tiles_per_split);
+}
+
+inline int64_t cmask_bytes(int n, int hc, int wc) { return al256((int64_t)8 * n * tiles_of(patches(hc, wc))); }
+
+// [score scratch | content tile masks | bank tile masks | partial scores | partial indices]
+inline int64_t guided_match_ws(int n, int S, int hc, int wc, int hs, int ws, int want) {
+  const int s = guided_splits(n, S, hc, wc, hs, ws, want, nullptr);
+  const int64_t one = al256((int64_t)4 * n * patches(hc, wc));
+  return one + cmask_bytes(n, hc, wc) + al256((int64_t)8 * bank_tiles(S, hs, ws)) +
+         (s > 1 ? 2 * al256((int64_t)4 * n * s * patches(hc, wc)) : 0);
+}
+
+int guided_match_launch(const float* ck, const float* sk, const float* inv, const uint8_t* cc, const uint8_t* sc,
+                        int* index, float* score, int n, int S, int c, int hc, int wc, int hs, int ws, int want,
+                        int flags, unsigned char* wsp, hipStream_t st) {
+  int tps = 0;
+  const int splits = guided_splits(n, S, hc, wc, hs, ws, want, &tps);
+  const int m = (int)patches(hc, wc), ns = (int)patches(hs, ws), ct = tiles_of(m), bt = tiles_of(ns);
+  const int64_t one = al256((int64_t)4 * n * m);
+  if (!score) score = (float*)wsp;
+  unsigned long long* cmask = (unsigned long long*)(wsp + one);
+  unsigned long long* bmask = (unsigned long long*)(wsp + one + cmask_bytes(n, hc, wc));
+  unsigned char* part = (unsigned char*)bmask + al256((int64_t)8 * S * bt);
+  hipLaunchKernelGGL(swap_class_mask_kernel, dim3(ct, n), dim3(64), 0, st, cc, cmask, m);
+  hipLaunchKernelGGL(swap_class_mask_kernel, dim3(bt, S), dim3(64), 0, st, sc, bmask, ns);
+  const Guide g{cc, sc, cmask, bmask, flags};
+  const dim3 grid(ct, splits, n);
+  auto kern = (wc >= 5 && ws >= 5) ? swap_match_kernel<2, Guide> : swap_match_kernel<3, Guide>;
+  if (splits == 1) {
+    hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, score, index, c, hc, wc, hs, ws, S, tps, g);
+  } else {
+    float* ps = (float*)part;
+    int* pi = (int*)(part + al256((int64_t)4 * n * splits * m));
+    hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, ps, pi, c, hc, wc, hs, ws, S, tps, g);
+    hipLaunchKernelGGL(swap_merge_kernel<-1>, dim3((m + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)ps,
+                       (const int*)pi, score, index, m, splits);
+  }
+  return (int)hipGetLastError();
+}
+
+int guided_gather_launch(const float* sv, const int* index, const float* content, float* out, int n, int S, int c,
+                         int hc, int wc, int hs, int ws, float alpha, hipStream_t st) {
+  hipLaunchKernelGGL(swap_gather_guided_kernel, dim3((hc * wc + kT - 1) / kT, (c + GC - 1) / GC, n), dim3(kT), 0, st, sv,
+                     index, content, out, c, hc, wc, hs, ws, S, alpha);
   return (int)hipGetLastError();
 }
 
@@ -502,6 +743,73 @@ int ast_style_swap_f32(const float* content_key, const float* style_key, const f
   e = match_launch(content_key, style_key, inv, index, score_or_null, n, ns, c, hc, wc, hs, ws, 0, scratch, st);
   if (e) return e;
   return gather_launch(style_value, index, content, out, n, ns, c, hc, wc, hs, ws, (float)alpha, st);
+}
+
+// ---- guided ----
+
+long long ast_patch_match_guided_workspace_bytes(int n, int s, int hc, int wc, int hs, int ws, int splits) {
+  const int e = bank_shape(n, s, hc, wc, hs, ws);
+  if (e) return e;
+  if (splits < 0) return AST_E_UNSUPPORTED;
+  return guided_match_ws(n, s, hc, wc, hs, ws, splits);
+}
+
+int ast_patch_match_guided_ex_f32(const float* content_key, const float* style_keys, const float* inv_norm,
+                                  const unsigned char* content_class, const unsigned char* style_class, int* index,
+                                  float* score_or_null, int n, int s, int c, int hc, int wc, int hs, int ws, int splits,
+                                  int flags, void* workspace, long long workspace_bytes, void* stream) {
+  if (!content_key || !style_keys || !inv_norm || !content_class || !style_class || !index || !workspace)
+    return AST_E_NULLPTR;
+  int e = bank_shape(n, s, hc, wc, hs, ws);
+  if (!e) e = chan_shape(c);
+  if (e) return e;
+  if (splits < 0 || (flags & ~AST_SWAP_NO_SKIP)) return AST_E_UNSUPPORTED;
+  if (workspace_bytes < guided_match_ws(n, s, hc, wc, hs, ws, splits)) return AST_E_SHAPE;
+  return guided_match_launch(content_key, style_keys, inv_norm, content_class, style_class, index, score_or_null, n, s,
+                             c, hc, wc, hs, ws, splits, flags, (unsigned char*)workspace, (hipStream_t)stream);
+}
+
+int ast_patch_gather_guided_f32(const float* style_values, const int* index, const float* content, float* out, int n,
+                                int s, int c, int hc, int wc, int hs, int ws, double alpha, void* stream) {
+  if (!style_values || !index || !content || !out) return AST_E_NULLPTR;
+  int e = bank_shape(n, s, hc, wc, hs, ws);
+  if (!e) e = chan_shape(c);
+  if (e) return e;
+  return guided_gather_launch(style_values, index, content, out, n, s, c, hc, wc, hs, ws, (float)alpha,
+                              (hipStream_t)stream);
+}
+
+// [inverse norms | index | the larger of the norms' and the guided match's scratch]
+long long ast_style_swap_guided_workspace_bytes(int n, int s, int hc, int wc, int hs, int ws) {
+  const int e = bank_shape(n, s, hc, wc, hs, ws);
+  if (e) return e;
+  const int64_t a = norms_ws(s, hs, ws), b = guided_match_ws(n, s, hc, wc, hs, ws, 0);
+  return al256((int64_t)4 * s * patches(hs, ws)) + al256((int64_t)4 * n * patches(hc, wc)) + (a > b ? a : b);
+}
+
+int ast_style_swap_guided_f32(const float* content_key, const float* style_keys, const float* style_values,
+                              const float* content, const unsigned char* content_class,
+                              const unsigned char* style_class, float* out, int* index_or_null, float* score_or_null,
+                              int n, int s, int c, int hc, int wc, int hs, int ws, double alpha, void* workspace,
+                              long long workspace_bytes, void* stream) {
+  if (!content_key || !style_keys || !style_values || !content || !content_class || !style_class || !out || !workspace)
+    return AST_E_NULLPTR;
+  int e = bank_shape(n, s, hc, wc, hs, ws);
+  if (!e) e = chan_shape(c);
+  if (e) return e;
+  if (workspace_bytes < ast_style_swap_guided_workspace_bytes(n, s, hc, wc, hs, ws)) return AST_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* w = (unsigned char*)workspace;
+  float* inv = (float*)w;
+  int* index = (int*)(w + al256((int64_t)4 * s * patches(hs, ws)));
+  unsigned char* scratch = (unsigned char*)index + al256((int64_t)4 * n * patches(hc, wc));
+  if (index_or_null) index = index_or_null;
+  e = norms_launch(style_keys, inv, s, c, hs, ws, (float*)scratch, st);
+  if (e) return e;
+  e = guided_match_launch(content_key, style_keys, inv, content_class, style_class, index, score_or_null, n, s, c, hc,
+                          wc, hs, ws, 0, 0, scratch, st);
+  if (e) return e;
+  return guided_gather_launch(style_values, index, content, out, n, s, c, hc, wc, hs, ws, (float)alpha, st);
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@ efdm                    -- (exact feature distribution matching)     d content =
 plane_sort              -- (segmented totalOrder sort of planes)     --
 wct                     -- (whitening and colouring transform)       raises NotImplementedError
 style_swap              -- (patch-matching style swap)               raises NotImplementedError
+style_swap_guided       -- (class-guided style swap over a bank)     raises NotImplementedError
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -766,7 +767,27 @@ def _style_swap_backward(ctx, g):
 register_autograd("ast_hip::style_swap", _style_swap_backward)
 
 
+@custom_op("ast_hip::style_swap_guided", mutates_args=())
+def style_swap_guided(content: Tensor, styles: Tensor, content_class: Tensor, style_class: Tensor, alpha: float,
+                      normalize: bool) -> Tensor:
+    """Style swap over a bank of styles, every content patch matched within its own class (uint8 class maps)."""
+    return ops.style_swap_guided(content, styles, content_class, style_class, alpha=alpha, normalize=normalize)
+
+
+@register_fake("ast_hip::style_swap_guided")
+def _(content, styles, content_class, style_class, alpha, normalize):
+    return torch.empty_like(content)
+
+
+def _style_swap_guided_backward(ctx, g):
+    raise NotImplementedError("ast_hip::style_swap_guided has no backward: style swap is inference-only")
+
+
+register_autograd("ast_hip::style_swap_guided", _style_swap_guided_backward)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "style_swap"]
+                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "style_swap",
+                  "style_swap_guided"]

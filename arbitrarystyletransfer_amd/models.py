@@ -446,7 +446,8 @@ class AdaINStyleTransfer(nn.Module):
     `transform="wct"` puts the whitening and colouring transform (WCT) there in the same way; it is
     inference-only (the forward raises NotImplementedError when a gradient is asked for).
     `stylize_swap` stylises by style swap (patch matching on the relu4_1 maps) with the same
-    encoder and decoder, whatever the transform.
+    encoder and decoder, whatever the transform; `stylize_swap_regions` is its guided form over a
+    bank of styles, steered by the label maps of `stylize_regions`.
     """
 
     TRANSFORMS = ("adain", "efdm", "wct")
@@ -503,6 +504,55 @@ class AdaINStyleTransfer(nn.Module):
             t = _ops().style_swap(f_c, f_s, float(alpha), bool(normalize))
         else:
             t = ops.style_swap(f_c, f_s, alpha=alpha, normalize=bool(normalize))
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
+
+    def stylize_swap_regions(self, content_img, style_imgs, labels=None, style_labels=None, alpha: float = 1.0,
+                             normalize: bool = False, preserve_color: bool = False):
+        """Guided style swap (ops.style_swap_guided on the relu4_1 maps): content_img [N, 3, H, W]
+        takes its patches from the bank of S styles style_imgs [S, 3, Hs, Ws] (shared by the batch),
+        steered by the label maps of stylize_regions. Inference only, whatever `transform`.
+
+        labels / style_labels: uint8 [N or S, H, W] (labels also [H, W]), at image or relu4_1
+        resolution; a patch has the label of its centre pixel (ops.patch_classes).
+        Neither: one class, every content patch takes its best patch from any of the styles.
+        labels only: region k takes style k; a label >= S passes the content through.
+        Both: a patch labelled k takes its best patch among those labelled k in any style ("sky
+        takes sky"); label 255 (any label >= ops.SWAP_MAX_CLASSES) in a style map removes the patch
+        from the bank, in the content map it passes the content through.
+        style_labels without labels: ValueError. normalize as stylize_swap, preserve_color as forward."""
+        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("stylize_swap_regions is inference-only; run it under torch.no_grad()")
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError("stylize_swap_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        if style_labels is not None and labels is None:
+            raise ValueError("style_labels without labels: give the content's label map too")
+        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
+        f_c = self.encoder(content_img)[0]
+        f_s = self.encoder(style_imgs)[0]
+        dev = f_c.device
+        if labels is None:
+            cc = torch.zeros((n, f_c.shape[2] - 2, f_c.shape[3] - 2), device=dev, dtype=torch.uint8)
+        else:
+            cc = ops.patch_classes(_feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(dev))
+        if style_labels is not None:
+            sc = ops.patch_classes(
+                _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(dev))
+        elif labels is None:
+            sc = torch.zeros((s, f_s.shape[2] - 2, f_s.shape[3] - 2), device=dev, dtype=torch.uint8)
+        else:
+            if s > ops.SWAP_MAX_CLASSES:
+                raise ValueError(f"labels alone assign style k to region k: at most {ops.SWAP_MAX_CLASSES} styles, "
+                                 f"got {s}")
+            sc = torch.arange(s, device=dev, dtype=torch.uint8).view(s, 1, 1).expand(
+                s, f_s.shape[2] - 2, f_s.shape[3] - 2).contiguous()
+        if _compiling():
+            t = _ops().style_swap_guided(f_c, f_s, cc, sc, float(alpha), bool(normalize))
+        else:
+            t = ops.style_swap_guided(f_c, f_s, cc, sc, alpha=alpha, normalize=bool(normalize))
         out = self.decoder(t)
         if preserve_color:
             return _luma_transfer(out, content_img)
@@ -629,7 +679,11 @@ def _feature_labels(labels, n, img_hw, feat_hw, name):
         raise ValueError(f"{name} must be at the image resolution {img_hw} or the feature resolution {feat_hw}, "
                          f"got {hw}")
     labels = labels.contiguous()
-    return labels if hw == feat_hw else ops.resize_labels(labels, feat_hw[0], feat_hw[1])
+    if hw == feat_hw:
+        return labels
+    if _compiling():
+        return _ops().resize_labels(labels, feat_hw[0], feat_hw[1])
+    return ops.resize_labels(labels, feat_hw[0], feat_hw[1])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -605,6 +605,129 @@ def style_swap(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, n
     return (out, index) if return_index else out
 
 
+# Guided style swap (csrc/swap.hip): a class >= SWAP_MAX_CLASSES takes no part in the match
+SWAP_MAX_CLASSES = 64
+_SWAP_NO_SKIP = 1   # AST_SWAP_NO_SKIP
+
+
+def patch_classes(labels: torch.Tensor) -> torch.Tensor:
+    """One class per 3x3 patch from a feature-resolution label map uint8 [B, h, w]: the label of the
+    patch's centre pixel, labels[:, 1:-1, 1:-1], as a dense uint8 [B, h - 2, w - 2]."""
+    if (not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3
+            or min(labels.shape[1:]) < 3):
+        raise HipOpError("patch_classes needs a uint8 label map [B, h, w] with sides of at least 3")
+    return labels[:, 1:-1, 1:-1].contiguous()
+
+
+def _bank_patches(s: int, hs: int, ws: int, what: str) -> int:
+    """S * (Hs - 2) * (Ws - 2), the number of style patches of a bank; it must stay below 2^31, the global
+    patch index being an int32."""
+    total = int(s) * (int(hs) - 2) * (int(ws) - 2)
+    if total >= 2 ** 31:
+        raise HipOpError(f"{what}: a bank of {s} styles {hs}x{ws} has {total} style patches, 2^31 or more")
+    return total
+
+
+def _swap_bank(a: torch.Tensor, b: torch.Tensor, na: str, nb: str, what: str):
+    """Content-side maps a [N, C, H, W] and a style bank b [S, C, Hs, Ws] (fp32, on one device, equal C,
+    sides of at least 3, S * (Hs - 2) * (Ws - 2) < 2^31): (a, b, n, S, c, ha, wa, hb, wb)."""
+    a, b = _dev(a, na), _dev(b, nb)
+    if (a.dim() != 4 or b.dim() != 4 or a.shape[1] != b.shape[1] or a.numel() == 0 or b.numel() == 0
+            or min(a.shape[2:]) < 3 or min(b.shape[2:]) < 3):
+        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C and sides of at least 3: "
+                         f"{na} {tuple(a.shape)} vs {nb} {tuple(b.shape)}")
+    if a.device != b.device:
+        raise HipOpError(f"{nb} is on {b.device}, {na} on {a.device}")
+    _bank_patches(b.shape[0], b.shape[2], b.shape[3], what)
+    n, c, ha, wa = (int(s) for s in a.shape)
+    return a, b, n, int(b.shape[0]), c, ha, wa, int(b.shape[2]), int(b.shape[3])
+
+
+def _swap_classes(cls, shape, device, name):
+    """A class map for `shape` patches: None (all 0) or a uint8 tensor of that shape on `device`."""
+    if cls is None:
+        return torch.zeros(shape, device=device, dtype=torch.uint8)
+    if (not isinstance(cls, torch.Tensor) or cls.dtype != torch.uint8 or tuple(cls.shape) != tuple(shape)
+            or cls.device != device):
+        raise HipOpError(f"{name} must be a uint8 tensor {tuple(shape)} on {device}")
+    return cls.contiguous()
+
+
+def patch_match_guided(content_key: torch.Tensor, style_keys: torch.Tensor, content_class: torch.Tensor,
+                       style_class: torch.Tensor, return_score: bool = False, _splits: int = 0, _skip: bool = True):
+    """patch_match under class guidance over a bank of styles. style_keys [S, C, Hs, Ws] is shared by the
+    batch; content_class uint8 [N, H - 2, W - 2] and style_class uint8 [S, Hs - 2, Ws - 2] give one class
+    per patch (None: all 0; patch_classes makes them from label maps). A content patch is matched
+    against the style patches of its own class only; a class >= SWAP_MAX_CLASSES takes no part. Returns
+    the global index s * (Hs - 2) * (Ws - 2) + jy * (Ws - 2) + jx, int32 [N, H - 2, W - 2] (the lowest on
+    equal scores), -1 with score -inf where a patch has no candidate. Scores are those of patch_match,
+    bit for bit. (content tile, bank tile) pairs that share no class are skipped. _splits as in
+    patch_match; _skip=False visits every tile (the same result)."""
+    ck, sk, n, s, c, hc, wc, hs, ws = _swap_bank(content_key, style_keys, "content_key", "style_keys",
+                                                 "patch_match_guided")
+    L, dev, st = lib(), ck.device, stream_ptr(ck.device)
+    cc = _swap_classes(content_class, (n, hc - 2, wc - 2), dev, "content_class")
+    sc = _swap_classes(style_class, (s, hs - 2, ws - 2), dev, "style_class")
+    nb = int(L.ast_patch_norms_workspace_bytes(s, hs, ws))
+    wsn = _ws_bytes(nb, "patch_norms workspace", dev)
+    inv = torch.empty((s, hs - 2, ws - 2), device=dev, dtype=torch.float32)
+    check(L.ast_patch_norms_f32(ptr(sk), ptr(inv), s, c, hs, ws, ptr(wsn), nb, st), "patch_norms")
+    mb = int(L.ast_patch_match_guided_workspace_bytes(n, s, hc, wc, hs, ws, int(_splits)))
+    wsm = _ws_bytes(mb, "patch_match_guided workspace", dev)
+    index = torch.empty((n, hc - 2, wc - 2), device=dev, dtype=torch.int32)
+    score = torch.empty((n, hc - 2, wc - 2), device=dev, dtype=torch.float32) if return_score else None
+    flops = 2 * n * (hc - 2) * (wc - 2) * s * (hs - 2) * (ws - 2) * 9 * c     # an upper bound: nothing skipped
+    check(_timed(f"patch_match_guided {c}ch {hc}x{wc} vs {s}x{hs}x{ws}", flops, dev,
+                 lambda: L.ast_patch_match_guided_ex_f32(
+                     ptr(ck), ptr(sk), ptr(inv), ptr(cc), ptr(sc), ptr(index), ptr(score), n, s, c, hc, wc, hs, ws,
+                     int(_splits), 0 if _skip else _SWAP_NO_SKIP, ptr(wsm), mb, st)), "patch_match_guided")
+    return (index, score) if return_score else index
+
+
+def patch_gather_guided(style_values: torch.Tensor, index: torch.Tensor, content: torch.Tensor, alpha: float = 1.0):
+    """patch_gather for the guided match: style_values [S, C, Hs, Ws] is the bank, index int32
+    [N, H - 2, W - 2] global over it; a negative index is "no match" and adds no term to the overlap
+    average; a pixel none of whose covering patches has a match is a copy of the content. One launch."""
+    c_, sv, n, s, c, hc, wc, hs, ws = _swap_bank(content, style_values, "content_map", "style_values",
+                                                 "patch_gather_guided")
+    if (not isinstance(index, torch.Tensor) or index.device != c_.device or index.dtype != torch.int32
+            or tuple(index.shape) != (n, hc - 2, wc - 2)):
+        raise HipOpError(f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
+    index = index.contiguous()
+    out = torch.empty_like(c_)
+    check(_timed(f"patch_gather_guided {c}ch {hc}x{wc}", -4 * 11 * c_.numel(), c_.device,
+                 lambda: lib().ast_patch_gather_guided_f32(ptr(sv), ptr(index), ptr(c_), ptr(out), n, s, c, hc, wc, hs,
+                                                           ws, float(alpha), stream_ptr(c_.device))),
+          "patch_gather_guided")
+    return out
+
+
+def style_swap_guided(content: torch.Tensor, styles: torch.Tensor, content_class: torch.Tensor = None,
+                      style_class: torch.Tensor = None, alpha: float = 1.0, normalize: bool = False,
+                      return_index: bool = False):
+    """Guided style swap (semantic style transfer by patches): every 3x3 patch of content [N, C, H, W] is
+    replaced by the most similar 3x3 patch of its own class from the bank styles [S, C, Hs, Ws]
+    (patch_match_guided), the overlaps of the matched patches are averaged and blended with the content
+    by alpha (patch_gather_guided); where nothing matched the content stays. Classes as in
+    patch_match_guided (None: all 0). normalize=True matches on mean_variance_norm of every map and
+    reconstructs from the raw style features, as style_swap does. return_index adds the int32 match."""
+    c_, s_, n, s, c, hc, wc, hs, ws = _swap_bank(content, styles, "content_map", "style_maps", "style_swap_guided")
+    cc = _swap_classes(content_class, (n, hc - 2, wc - 2), c_.device, "content_class")
+    sc = _swap_classes(style_class, (s, hs - 2, ws - 2), c_.device, "style_class")
+    ck, sk = (mean_variance_norm(c_), mean_variance_norm(s_)) if normalize else (c_, s_)
+    L = lib()
+    nbytes = int(L.ast_style_swap_guided_workspace_bytes(n, s, hc, wc, hs, ws))
+    wsb = _ws_bytes(nbytes, "style_swap_guided workspace", c_.device)
+    out = torch.empty_like(c_)
+    index = torch.empty((n, hc - 2, wc - 2), device=c_.device, dtype=torch.int32) if return_index else None
+    flops = 2 * n * (hc - 2) * (wc - 2) * s * (hs - 2) * (ws - 2) * 9 * c     # an upper bound: nothing skipped
+    check(_timed(f"style_swap_guided {c}ch {hc}x{wc} vs {s}x{hs}x{ws}", flops, c_.device,
+                 lambda: L.ast_style_swap_guided_f32(
+                     ptr(ck), ptr(sk), ptr(s_), ptr(c_), ptr(cc), ptr(sc), ptr(out), ptr(index), None, n, s, c, hc, wc,
+                     hs, ws, float(alpha), ptr(wsb), nbytes, stream_ptr(c_.device))), "style_swap_guided")
+    return (out, index) if return_index else out
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

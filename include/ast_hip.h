@@ -321,6 +321,49 @@ int ast_style_swap_f32(const float* content_key, const float* style_key, const f
                        int n, int ns, int c, int hc, int wc, int hs, int ws, double alpha,
                        void* workspace, long long workspace_bytes, void* stream);
 
+/* Guided style swap (semantic / "neural doodle" patch transfer: Champandard 2016; Li & Wand CVPR 2016;
+ * csrc/swap.hip): the patch match above, constrained to style patches of the content patch's own
+ * class, over a bank of styles.
+ * Inputs: content key ck and content x [n, c, hc, wc] as above; the style bank, keys sk and values sv
+ * [s, c, hs, ws], s >= 1, shared by the batch. Ns = (hs - 2)(ws - 2); the global style patch index is
+ * j = st Ns + jy (ws - 2) + jx for style st; s Ns < 2^31. Limits as above, with s in place of ns.
+ * Classes, one per patch: content_class uint8 [n, hc - 2, wc - 2], style_class uint8 [s, hs - 2, ws - 2].
+ * A class >= AST_SWAP_MAX_CLASSES takes no part: such a content patch gets no match, such a style patch
+ * is never a candidate.
+ * Match: score(i, j) is the score above, in bits (the same fma chain and inverse norm); index(i) = the
+ * j of maximal score among the j with style_class(j) == content_class(i) < AST_SWAP_MAX_CLASSES; the
+ * lowest global j wins on equal scores (so the lower style of the bank); a NaN never wins; without an
+ * admissible candidate, or with none above -inf, index -1 and score -inf. With one class and s = 1 this
+ * is the unguided match except for that -1 (there 0).
+ * Reconstruct: the overlap average above over the covering content patches whose index is >= 0, in
+ * ascending (dy, dx) order, cnt counting those; a pixel with cnt = 0 returns x[y, x] in bits, whatever
+ * alpha. A negative index given to ast_patch_gather_guided_f32 is "no match"; one >= s Ns is clamped.
+ * Stages: ast_patch_norms_f32 with ns = s gives the bank's inverse norms; the guided match first writes
+ * one 64-bit class-presence mask per 64-patch content tile and per bank tile (a bank tile lies within
+ * one style) into its workspace, then a workgroup visits a bank tile only if the two masks meet --
+ * the work is the sum over classes of content tiles x bank tiles holding the class instead of all pairs
+ * --; flag AST_SWAP_NO_SKIP of the _ex entry visits every tile (a test hook, like splits). The result
+ * does not depend on the flag or on splits, bit for bit. ast_style_swap_guided_f32 is norms, guided
+ * match, guided gather, bit for bit. Errors as above; s Ns >= 2^31 is AST_E_SHAPE, an unknown flag
+ * AST_E_UNSUPPORTED. No atomics, no host synchronisation, no allocation. */
+#define AST_SWAP_MAX_CLASSES 64
+#define AST_SWAP_NO_SKIP 1
+long long ast_patch_match_guided_workspace_bytes(int n, int s, int hc, int wc, int hs, int ws, int splits);
+int ast_patch_match_guided_ex_f32(const float* content_key, const float* style_keys, const float* inv_norm,
+                                  const unsigned char* content_class, const unsigned char* style_class,
+                                  int* index, float* score_or_null, int n, int s, int c, int hc, int wc,
+                                  int hs, int ws, int splits, int flags, void* workspace,
+                                  long long workspace_bytes, void* stream);
+int ast_patch_gather_guided_f32(const float* style_values, const int* index, const float* content, float* out,
+                                int n, int s, int c, int hc, int wc, int hs, int ws, double alpha,
+                                void* stream);
+long long ast_style_swap_guided_workspace_bytes(int n, int s, int hc, int wc, int hs, int ws);
+int ast_style_swap_guided_f32(const float* content_key, const float* style_keys, const float* style_values,
+                              const float* content, const unsigned char* content_class,
+                              const unsigned char* style_class, float* out, int* index_or_null,
+                              float* score_or_null, int n, int s, int c, int hc, int wc, int hs, int ws,
+                              double alpha, void* workspace, long long workspace_bytes, void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
