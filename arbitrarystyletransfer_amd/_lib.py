@@ -56,6 +56,12 @@ SIGNATURES = {
     "ast_wct_apply_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _ll, _d, _p, _ll, _p]),
     "ast_wct_workspace_bytes": (_ll, [_i, _i, _i, _ll, _ll]),
     "ast_wct_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _f, _i, _p, _ll, _p]),
+    "ast_wct_region_cov_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_wct_region_cov_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _ll, _p]),
+    "ast_wct_region_apply_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_wct_region_apply_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
+    "ast_wct_regions_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "ast_wct_regions_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _f, _i, _p, _ll, _p]),
     "ast_patch_norms_workspace_bytes": (_ll, [_i, _i, _i]),
     "ast_patch_norms_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _ll, _p]),
     "ast_patch_match_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i]),

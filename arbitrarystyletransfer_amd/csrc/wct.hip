@@ -10,6 +10,8 @@
 //   apply         T = S^(1/2)_style . S^(-1/2)_content, then out = alpha (T (x - mu_c) + mu_s) +
 //                 (1 - alpha) x as one GEMM with the centring staged into the operand and the bias
 //                 and blend in the epilogue
+// The regional form (ast_wct_regions_f32 and its stages, further down) bins the pixels of a label map
+// by region once and runs the same covariance and apply products through that permutation.
 // Every product is v_mfma_f32_32x32x2_f32 on fp32 operands (the tile of mbtrain.hip's gemm_kernel:
 // 64x64 per workgroup, 4 waves x 32x32, K in chunks of 32 through LDS with the next chunk's loads in
 // flight). Tiles past a matrix edge are zero-filled while staging, so any C in 1..1024 and any
@@ -62,11 +64,15 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
 // in memory -- m for A, n for a k-contiguous B, k for an n-contiguous one -- and are subtracted while
 // staging; elements past M, N or kend are staged as 0, not as -mu.
 // Accumulator element i of a lane is row wm * 32 + (i & 3) + 8 (i >> 2) + 4 h, column wn * 32 + r.
+// GATHER (the regional kernels): the pixel axis of the map -- k of both operands when BKFAST, else the
+// n of B -- is read through idx, so logical pixel j is element idx[j] of its plane; kbeg, kend, n0 and
+// N then count logical pixels. Without it idx is unused and the code is the ungathered one.
 // ------------------------------------------------------------------------------------------------
-template <bool BKFAST>
+template <bool BKFAST, bool GATHER = false>
 __device__ __forceinline__ f32x16 tile_mm(const float* __restrict__ A, int64_t lda, const float* __restrict__ amu,
                                           const float* __restrict__ B, int64_t ldb, const float* __restrict__ bmu,
-                                          int M, int N, int m0, int n0, int kbeg, int kend, float* As, float* Bs) {
+                                          int M, int N, int m0, int n0, int kbeg, int kend, float* As, float* Bs,
+                                          const int* __restrict__ idx = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
   const int wm = wave & 1, wn = wave >> 1;
   const int k_f = tid & 31, r_f = tid >> 5;  // k-contiguous operand: k = k_f, row = r_f + 8 i
@@ -78,25 +84,29 @@ __device__ __forceinline__ f32x16 tile_mm(const float* __restrict__ A, int64_t l
     am[i] = (amu && gm < M) ? amu[gm] : 0.f;
     bm[i] = (BKFAST && bmu && gn < N) ? bmu[gn] : 0.f;
   }
+  int pn = n0 + n_f;  // the n-contiguous B's column in memory
+  if constexpr (GATHER && !BKFAST) pn = pn < N ? idx[pn] : 0;
   auto load = [&](int k0) {
     const int gk = k0 + k_f;
+    int pk = gk;        // the k-contiguous operands' k in memory
+    if constexpr (GATHER && BKFAST) pk = gk < kend ? idx[gk] : 0;
 #pragma unroll
     for (int i = 0; i < WL; ++i) {
       const int gm = m0 + r_f + 8 * i;
-      ra[i] = (gk < kend && gm < M) ? A[(int64_t)gm * lda + gk] - am[i] : 0.f;
+      ra[i] = (gk < kend && gm < M) ? A[(int64_t)gm * lda + pk] - am[i] : 0.f;
     }
     if (BKFAST) {
 #pragma unroll
       for (int i = 0; i < WL; ++i) {
         const int gn = n0 + r_f + 8 * i;
-        rb[i] = (gk < kend && gn < N) ? B[(int64_t)gn * ldb + gk] - bm[i] : 0.f;
+        rb[i] = (gk < kend && gn < N) ? B[(int64_t)gn * ldb + pk] - bm[i] : 0.f;
       }
     } else {
       const int gn = n0 + n_f;
 #pragma unroll
       for (int i = 0; i < WL; ++i) {
         const int gk2 = k0 + k_s + 4 * i;
-        rb[i] = (gk2 < kend && gn < N) ? B[(int64_t)gk2 * ldb + gn] - (bmu ? bmu[gk2] : 0.f) : 0.f;
+        rb[i] = (gk2 < kend && gn < N) ? B[(int64_t)gk2 * ldb + pn] - (bmu ? bmu[gk2] : 0.f) : 0.f;
       }
     }
   };
@@ -316,21 +326,292 @@ __global__ __launch_bounds__(kT) void wct_apply_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side: argument checks, workspace layouts, launch sequences
+// Regional WCT: the pixels of a sample are binned by region once (a permutation of the pixel indices
+// and K counts); every later kernel reads its pixel axis through that permutation and so does the
+// MFMA work of the unmasked transform, whatever K. Bin K holds the pass-through pixels (label >= K).
+// No grid size depends on the labels: a workgroup that finds nothing to do in the counts exits
+// before its first barrier (the counts are uniform over a workgroup, so all its threads leave).
 // ------------------------------------------------------------------------------------------------
 
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-inline bool eps_ok(float e) { return e >= 1e-4f && e <= 1.f; }
-inline int tiles_of(int c) { return (c + WT - 1) / WT; }
-
-// K split of the covariance: chunks of at least 64 pixels (a multiple of 32), at most kMaxSplits.
-inline int cov_splits(int64_t m, int* kchunk) {
+// K split of the covariance: chunks of at least 64 pixels (a multiple of 32), at most kMaxSplits. The
+// host sizes the unmasked launch with it; a regional workgroup evaluates it for its region's size.
+__host__ __device__ inline int cov_splits(int64_t m, int* kchunk) {
   int64_t s = (m + 63) / 64;
   if (s > kMaxSplits) s = kMaxSplits;
   const int64_t kc = (((m + s - 1) / s) + 31) / 32 * 32;
   if (kchunk) *kchunk = (int)kc;
   return (int)((m + kc - 1) / kc);
 }
+
+constexpr int kBins = AST_MAX_REGIONS + 1;
+constexpr int64_t kMaxRegionM = (int64_t)1 << 24;  // pixels per plane: one workgroup bins a sample
+
+// grid (samples): perm[b] = the pixel indices of sample b ordered by (min(label, K), pixel index),
+// count[b, k] = the pixels labelled k. Thread t owns the contiguous chunk [t * chunk, (t + 1) * chunk)
+// of the pixels: it counts its chunk per bin, the kBins * 256 counts are scanned in (bin, thread)
+// order through LDS, and it then writes its pixels at its offsets. Integer sums, no atomics.
+__global__ __launch_bounds__(kT) void wct_bin_kernel(const unsigned char* __restrict__ labels, int* __restrict__ perm,
+                                                    int* __restrict__ count, int M, int K) {
+  __shared__ int sc[kBins * kT];
+  __shared__ int wtot[kT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned char* L = labels + (int64_t)blockIdx.x * M;
+  int* P = perm + (int64_t)blockIdx.x * M;
+  const int chunk = (M + kT - 1) / kT;
+  const int beg = min(tid * chunk, M), end = min(beg + chunk, M);
+  int c[kBins];
+#pragma unroll
+  for (int j = 0; j < kBins; ++j) c[j] = 0;
+  for (int i = beg; i < end; ++i) {
+    const int l = min((int)L[i], K);
+#pragma unroll
+    for (int j = 0; j < kBins; ++j) c[j] += l == j;
+  }
+#pragma unroll
+  for (int j = 0; j < kBins; ++j) sc[j * kT + tid] = c[j];
+  __syncthreads();
+  // exclusive scan of sc[0 .. kBins * kT): thread t takes entries [t * kBins, (t + 1) * kBins)
+  int loc[kBins], tot = 0;
+#pragma unroll
+  for (int j = 0; j < kBins; ++j) {
+    loc[j] = tot;
+    tot += sc[tid * kBins + j];
+  }
+  int inc = tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) wtot[wave] = inc;
+  __syncthreads();
+  int base = inc - tot;
+  for (int i = 0; i < wave; ++i) base += wtot[i];
+#pragma unroll
+  for (int j = 0; j < kBins; ++j) sc[tid * kBins + j] = base + loc[j];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kBins; ++j) c[j] = sc[j * kT + tid];
+  for (int i = beg; i < end; ++i) {
+    const int l = min((int)L[i], K);
+    int pos = 0;
+#pragma unroll
+    for (int j = 0; j < kBins; ++j) {
+      pos = l == j ? c[j] : pos;
+      c[j] += l == j;
+    }
+    P[pos] = i;
+  }
+  if (tid < K) count[blockIdx.x * K + tid] = sc[(tid + 1) * kT] - sc[tid * kT];
+}
+
+// The first pixel of region k in the permutation of its sample.
+__device__ __forceinline__ int bin_offset(const int* __restrict__ cnt, int k) {
+  int off = 0;
+  for (int j = 0; j < k; ++j) off += cnt[j];
+  return off;
+}
+
+// grid (channels, samples * K): wct_mean_kernel on the region's pixels in ascending pixel index; 0 for a
+// region of fewer than 2 pixels.
+__global__ __launch_bounds__(kT) void wct_region_mean_kernel(const float* __restrict__ x, const int* __restrict__ perm,
+                                                            const int* __restrict__ count, float* __restrict__ mean,
+                                                            int C, int M, int K) {
+  __shared__ float sh[kT / 64];
+  const int z = blockIdx.y, b = z / K, k = z % K;
+  const int* cnt = count + b * K;
+  const int mk = cnt[k];
+  float* out = mean + (int64_t)z * C + blockIdx.x;
+  if (mk < 2) {
+    if (threadIdx.x == 0) *out = 0.f;
+    return;
+  }
+  const int* idx = perm + (int64_t)b * M + bin_offset(cnt, k);
+  const float* p = x + ((int64_t)b * C + blockIdx.x) * M;
+  const float x0 = p[idx[0]];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < mk; i += kT) s += p[idx[i]] - x0;
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) *out = x0 + s / (float)mk;
+}
+
+// grid (upper-triangle tile pairs, region_slots(M), samples * K): wct_cov_kernel on the region's gathered
+// map, with the split count and chunk that cov_splits gives for the region's own size (never more than
+// region_slots(M), the bound over every region size up to M).
+__global__ __launch_bounds__(kT) void wct_region_cov_kernel(const float* __restrict__ x, const int* __restrict__ perm,
+                                                           const int* __restrict__ count, const float* __restrict__ mean,
+                                                           float* __restrict__ part, int C, int M, int K) {
+  __shared__ float As[WK * WP];
+  __shared__ float Bs[WK * WP];
+  const int z = blockIdx.z, b = z / K, k = z % K, ks = blockIdx.y;
+  const int* cnt = count + b * K;
+  const int mk = cnt[k];
+  if (mk < 2) return;
+  int kchunk = 0;
+  if (ks >= cov_splits(mk, &kchunk)) return;
+  int p = blockIdx.x, ti = 0, rowlen = (C + WT - 1) / WT;
+  while (p >= rowlen) {
+    p -= rowlen;
+    ++ti;
+    --rowlen;
+  }
+  const int tj = ti + p;
+  const int kbeg = ks * kchunk, kend = min(kbeg + kchunk, mk);
+  const float* X = x + (int64_t)b * C * M;
+  const float* mu = mean + (int64_t)z * C;
+  const f32x16 acc = tile_mm<true, true>(X, M, mu, X, M, mu, C, C, ti * WT, tj * WT, kbeg, kend, As, Bs,
+                                         perm + (int64_t)b * M + bin_offset(cnt, k));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int wm = wave & 1, wn = wave >> 1;
+  float* P = part + (((int64_t)z * gridDim.y + ks) * gridDim.x + blockIdx.x) * (WT * WT) + wn * 32 + r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) P[(wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * WT] = acc[i];
+}
+
+// grid (tile pairs, samples * K): wct_cov_reduce_kernel over the region's own splits (`slots` per region
+// in the workspace); the identity for a region of fewer than 2 pixels.
+__global__ __launch_bounds__(kT) void wct_region_reduce_kernel(const float* __restrict__ part,
+                                                              const int* __restrict__ count, float* __restrict__ cov,
+                                                              int C, int slots) {
+  int p = blockIdx.x, ti = 0, rowlen = (C + WT - 1) / WT;
+  while (p >= rowlen) {
+    p -= rowlen;
+    ++ti;
+    --rowlen;
+  }
+  const int tj = ti + p, z = blockIdx.y, mk = count[z];
+  const int splits = mk < 2 ? 0 : cov_splits(mk, nullptr);
+  const float denom = (float)(mk - 1);
+  const int64_t tile = WT * WT, sstride = (int64_t)gridDim.x * tile;
+  const float* P = part + (int64_t)z * slots * sstride + (int64_t)blockIdx.x * tile;
+  float* S = cov + (int64_t)z * C * C;
+  for (int e = threadIdx.x; e < WT * WT; e += kT) {
+    const int i = ti * WT + e / WT, j = tj * WT + e % WT;
+    if (i >= C || j >= C || (ti == tj && i > j)) continue;
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += P[k * sstride + e];
+    s = splits ? s / denom : (i == j ? 1.f : 0.f);
+    S[(int64_t)i * C + j] = s;
+    S[(int64_t)j * C + i] = s;
+  }
+}
+
+// grid (samples * K): wct_ridge_kernel; the identity of an invalid region stays as it is.
+__global__ __launch_bounds__(kT) void wct_region_ridge_kernel(float* __restrict__ cov, const int* __restrict__ count,
+                                                             int C, float eps_rel) {
+  __shared__ float sh[kT / 64];
+  if (count[blockIdx.x] < 2) return;
+  float* S = cov + (int64_t)blockIdx.x * C * C;
+  float t = 0.f;
+  for (int i = threadIdx.x; i < C; i += kT) t += S[(int64_t)i * C + i];
+  t = block_sum(t, sh);
+  const float eps = eps_rel * fmaxf(t / (float)C, kTraceFloor);
+  for (int i = threadIdx.x; i < C; i += kT) S[(int64_t)i * C + i] += eps;
+}
+
+// grid (ceil((C * C + C) / 256), samples * K): the colouring matrix cmix[b, k] = sum_s w_s sroot[s] and
+// the target mean mmix[b, k] = sum_s w_s smean[s] over the styles of non-zero weight in ascending s (the
+// first term a product, the later ones fmaf), and valid[b, k]: the content region has 2 pixels or more,
+// some weight is non-zero, and (scount given) so has region k of every style used. A style row is s, or
+// s * K + k with `regional` statistics.
+__global__ __launch_bounds__(kT) void wct_region_mix_kernel(const float* __restrict__ sroot, const float* __restrict__ smean,
+                                                           const float* __restrict__ mix, const int* __restrict__ ccount,
+                                                           const int* __restrict__ scount, float* __restrict__ cmix,
+                                                           float* __restrict__ mmix, int* __restrict__ valid, int C, int K,
+                                                           int S, int mix_stride, int regional) {
+  const int z = blockIdx.y, b = z / K, k = z % K;
+  const float* w = mix + (int64_t)b * mix_stride + k * S;
+  const int64_t cc = (int64_t)C * C, e = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (e == 0) {
+    int ok = ccount[z] >= 2, used = 0;
+    for (int s = 0; s < S; ++s) {
+      if (w[s] == 0.f) continue;
+      used = 1;
+      if (scount && scount[s * K + k] < 2) ok = 0;
+    }
+    valid[z] = ok & used;
+  }
+  if (e >= cc + C) return;
+  const bool mat = e < cc;
+  const float* src = mat ? sroot : smean;
+  const int64_t stride = mat ? cc : C, el = mat ? e : e - cc;
+  float acc = 0.f;
+  bool first = true;
+  for (int s = 0; s < S; ++s) {
+    const float ws = w[s];
+    if (ws == 0.f) continue;
+    const float y = src[(int64_t)(regional ? s * K + k : s) * stride + el];
+    acc = first ? ws * y : __fmaf_rn(ws, y, acc);
+    first = false;
+  }
+  (mat ? cmix + (int64_t)z * cc : mmix + (int64_t)z * C)[el] = acc;
+}
+
+// grid (ceil(M / 64) + K + 1 column tiles, channel tiles, samples). A column tile is 64 consecutive
+// entries of one bin of the permutation, found from the counts; tiles past the last bin exit. A tile of
+// a valid region is wct_apply_kernel's on the gathered columns, scattered back through the
+// permutation; a tile of the pass-through bin or of an invalid region copies its pixels. Every output
+// element is written exactly once.
+__global__ __launch_bounds__(kT) void wct_region_apply_kernel(const float* __restrict__ T, const float* __restrict__ x,
+                                                             const int* __restrict__ perm, const int* __restrict__ count,
+                                                             const int* __restrict__ valid, const float* __restrict__ cmu,
+                                                             const float* __restrict__ mmix, float* __restrict__ out,
+                                                             int C, int M, int K, float alpha) {
+  __shared__ float As[WK * WP];
+  __shared__ float Bs[WK * WP];
+  const int b = blockIdx.z;
+  const int* cnt = count + b * K;
+  int rest = M;
+  for (int j = 0; j < K; ++j) rest -= cnt[j];
+  int t = blockIdx.x, bin = 0, off = 0, nb = 0;
+  for (; bin <= K; ++bin) {
+    nb = bin < K ? cnt[bin] : rest;
+    const int nt = (nb + WT - 1) / WT;
+    if (t < nt) break;
+    t -= nt;
+    off += nb;
+  }
+  if (bin > K) return;
+  const int z = b * K + bin, m0 = blockIdx.y * WT, n0 = t * WT;
+  const int* idx = perm + (int64_t)b * M + off;
+  const float* X = x + (int64_t)b * C * M;
+  float* O = out + (int64_t)b * C * M;
+  if (bin == K || valid[z] == 0) {
+    const int j = n0 + (threadIdx.x & 63);
+    if (j >= nb) return;
+    const int64_t pix = idx[j];
+#pragma unroll
+    for (int i = 0; i < WT / (kT / 64); ++i) {
+      const int m = m0 + (threadIdx.x >> 6) + (kT / 64) * i;
+      if (m < C) O[(int64_t)m * M + pix] = X[(int64_t)m * M + pix];
+    }
+    return;
+  }
+  const f32x16 acc = tile_mm<false, true>(T + (int64_t)z * C * C, C, nullptr, X, M, cmu + (int64_t)z * C, C, nb, m0, n0,
+                                          0, C, As, Bs, idx);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int j = n0 + (wave >> 1) * 32 + r;
+  if (j >= nb) return;
+  const int64_t n = idx[j];
+  const float* ms = mmix + (int64_t)z * C;
+  O += n;
+  const float beta = 1.f - alpha;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int m = m0 + (wave & 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+    if (m >= C) continue;
+    const float v = acc[i] + ms[m];
+    O[(int64_t)m * M] = alpha * v + beta * X[(int64_t)m * M + n];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side: argument checks, workspace layouts, launch sequences
+// ------------------------------------------------------------------------------------------------
+
+inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+inline bool eps_ok(float e) { return e >= 1e-4f && e <= 1.f; }
+inline int tiles_of(int c) { return (c + WT - 1) / WT; }
 
 inline int default_iters(int c, float eps_rel) {
   return (int)ceil(log((double)c / (double)eps_rel) / log(2.25)) + 5;
@@ -407,6 +688,91 @@ int pair_shape(int n, int ns, int c, int64_t mc, int64_t ms) {
 }
 
 inline int64_t max3(int64_t a, int64_t b, int64_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+
+// ---- regional WCT ----
+
+// AST_OK, or the code that rejects (samples, channels, plane, regions) of a labelled map
+inline int region_shape(int n, int c, int h, int w, int regions) {
+  if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || (int64_t)h * w > kMaxRegionM || regions < 1 ||
+      regions > AST_MAX_REGIONS || (int64_t)n * regions > 32767)
+    return AST_E_SHAPE;
+  return c > kMaxC ? AST_E_UNSUPPORTED : AST_OK;
+}
+
+inline int64_t perm_ws(int n, int64_t m) { return al256((int64_t)4 * n * m); }
+// The most splits that a region of a plane of m pixels can take: max of cov_splits(mk) over mk <= m.
+// cov_splits is ceil(mk / 64) up to 448 pixels and kMaxSplits from 449 to 512, but dips below that
+// beyond (6 at 513: chunks of 96), so cov_splits(m) itself is no bound.
+inline int region_slots(int64_t m) { return m >= 64 * (kMaxSplits - 1) + 1 ? kMaxSplits : cov_splits(m, nullptr); }
+
+inline int64_t region_part_ws(int n, int c, int64_t m, int k) {
+  const int t = tiles_of(c);
+  return al256((int64_t)4 * n * k * region_slots(m) * (t * (t + 1) / 2) * (WT * WT));
+}
+inline int64_t region_cov_ws(int n, int c, int64_t m, int k) { return perm_ws(n, m) + region_part_ws(n, c, m, k); }
+
+// [valid | mmix | cmix | T] of the apply stage, after the permutation and the counts
+inline int64_t region_mix_ws(int n, int c, int k) {
+  return al256((int64_t)4 * n * k) + al256((int64_t)4 * n * k * c) + 2 * al256((int64_t)4 * n * k * c * c);
+}
+inline int64_t region_apply_ws(int n, int c, int64_t m, int k) {
+  return perm_ws(n, m) + al256((int64_t)4 * n * k) + region_mix_ws(n, c, k);
+}
+
+int bin_launch(const unsigned char* labels, int* perm, int* count, int n, int64_t m, int k, hipStream_t st) {
+  hipLaunchKernelGGL(wct_bin_kernel, dim3(n), dim3(kT), 0, st, labels, perm, count, (int)m, k);
+  return (int)hipGetLastError();
+}
+
+// mean [n, k, c] and cov [n, k, c, c] from a binned map
+int region_cov_launch(const float* x, const int* perm, const int* count, float* mean, float* cov, int n, int c,
+                      int64_t m, int k, float eps_rel, float* part, hipStream_t st) {
+  const int slots = region_slots(m), t = tiles_of(c), pairs = t * (t + 1) / 2;
+  hipLaunchKernelGGL(wct_region_mean_kernel, dim3(c, n * k), dim3(kT), 0, st, x, perm, count, mean, c, (int)m, k);
+  hipLaunchKernelGGL(wct_region_cov_kernel, dim3(pairs, slots, n * k), dim3(kT), 0, st, x, perm, count,
+                     (const float*)mean, part, c, (int)m, k);
+  hipLaunchKernelGGL(wct_region_reduce_kernel, dim3(pairs, n * k), dim3(kT), 0, st, (const float*)part, count, cov, c,
+                     slots);
+  hipLaunchKernelGGL(wct_region_ridge_kernel, dim3(n * k), dim3(kT), 0, st, cov, count, c, eps_rel);
+  return (int)hipGetLastError();
+}
+
+// out from a binned content map and the parts; ws = [valid | mmix | cmix | T]
+int region_apply_launch(const float* content, const int* perm, const int* count, const float* cmean, const float* ciroot,
+                        const float* smean, const float* sroot, const float* mix, const int* scount, float* out, int n,
+                        int c, int64_t m, int k, int s, int mix_n, int regional, float alpha, unsigned char* ws,
+                        hipStream_t st) {
+  const int64_t cc = (int64_t)c * c;
+  const int t = tiles_of(c);
+  int* valid = (int*)ws;
+  float* mmix = (float*)(ws + al256((int64_t)4 * n * k));
+  float* cmix = (float*)((unsigned char*)mmix + al256((int64_t)4 * n * k * c));
+  float* T = (float*)((unsigned char*)cmix + al256((int64_t)4 * n * k * cc));
+  hipLaunchKernelGGL(wct_region_mix_kernel, dim3((unsigned)((cc + c + kT - 1) / kT), n * k), dim3(kT), 0, st, sroot, smean,
+                     mix, count, scount, cmix, mmix, valid, c, k, s, mix_n == 1 ? 0 : k * s, regional);
+  hipLaunchKernelGGL(wct_sq_gemm_kernel<kPlain>, dim3(t, t, n * k), dim3(kT), 0, st, (const float*)cmix, ciroot, T, cc,
+                     cc, c, n * k);
+  hipLaunchKernelGGL(wct_region_apply_kernel, dim3((unsigned)((m + WT - 1) / WT + k + 1), t, n), dim3(kT), 0, st,
+                     (const float*)T, content, perm, count, (const int*)valid, cmean, (const float*)mmix, out, c, (int)m,
+                     k, alpha);
+  return (int)hipGetLastError();
+}
+
+inline int mix_shape(int n, int styles, int mix_n) {
+  return (styles < 1 || styles > AST_MAX_STYLE_ROWS || (mix_n != 1 && mix_n != n)) ? AST_E_SHAPE : AST_OK;
+}
+
+// the checks of the whole op, in the order of the stages
+int regions_shape(int n, int c, int hc, int wc, int regions, int styles, int hs, int ws, int style_regional, int mix_n) {
+  int e = region_shape(n, c, hc, wc, regions);
+  if (e) return e;
+  e = mix_shape(n, styles, mix_n);
+  if (e) return e;
+  if (hs <= 0 || ws <= 0) return AST_E_SHAPE;
+  e = style_regional ? region_shape(styles, c, hs, ws, regions) : cov_shape(styles, c, (int64_t)hs * ws);
+  if (e) return e;
+  return n * regions + styles * (style_regional ? regions : 1) > 32767 ? AST_E_SHAPE : AST_OK;
+}
 
 }  // namespace
 
@@ -506,6 +872,120 @@ int ast_wct_f32(const float* content, const float* style, float* out, int n, int
   if (e) return e;
   return apply_launch(content, mean, mean + (int64_t)n * c, root + n * cc, iroot, out, n, ns, c, mc, (float)alpha,
                       (float*)scratch, st);
+}
+
+// ---- regional WCT ----
+
+long long ast_wct_region_cov_workspace_bytes(int n, int c, int h, int w, int regions) {
+  const int e = region_shape(n, c, h, w, regions);
+  return e ? e : region_cov_ws(n, c, (int64_t)h * w, regions);
+}
+
+int ast_wct_region_cov_f32(const float* x, const unsigned char* labels, float* mean, float* cov, int* count, int n,
+                           int c, int h, int w, int regions, float eps_rel, void* workspace,
+                           long long workspace_bytes, void* stream) {
+  if (!x || !labels || !mean || !cov || !count || !workspace) return AST_E_NULLPTR;
+  int e = region_shape(n, c, h, w, regions);
+  if (e) return e;
+  if (!eps_ok(eps_rel)) return AST_E_UNSUPPORTED;
+  const int64_t m = (int64_t)h * w;
+  if (workspace_bytes < region_cov_ws(n, c, m, regions)) return AST_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  int* perm = (int*)workspace;
+  e = bin_launch(labels, perm, count, n, m, regions, st);
+  if (e) return e;
+  return region_cov_launch(x, perm, count, mean, cov, n, c, m, regions, eps_rel,
+                           (float*)((unsigned char*)workspace + perm_ws(n, m)), st);
+}
+
+long long ast_wct_region_apply_workspace_bytes(int n, int c, int h, int w, int regions) {
+  const int e = region_shape(n, c, h, w, regions);
+  return e ? e : region_apply_ws(n, c, (int64_t)h * w, regions);
+}
+
+int ast_wct_region_apply_f32(const float* content, const unsigned char* labels, const float* content_mean,
+                             const float* content_isqrt, const float* style_mean, const float* style_sqrt,
+                             const float* mix, const int* style_count_or_null, float* out, int n, int c, int h, int w,
+                             int regions, int styles, int mix_n, int style_regional, double alpha, void* workspace,
+                             long long workspace_bytes, void* stream) {
+  if (!content || !labels || !content_mean || !content_isqrt || !style_mean || !style_sqrt || !mix || !out || !workspace)
+    return AST_E_NULLPTR;
+  int e = region_shape(n, c, h, w, regions);
+  if (e) return e;
+  e = mix_shape(n, styles, mix_n);
+  if (e) return e;
+  const int64_t m = (int64_t)h * w;
+  if (workspace_bytes < region_apply_ws(n, c, m, regions)) return AST_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* wsp = (unsigned char*)workspace;
+  int* perm = (int*)wsp;
+  int* count = (int*)(wsp + perm_ws(n, m));
+  e = bin_launch(labels, perm, count, n, m, regions, st);
+  if (e) return e;
+  return region_apply_launch(content, perm, count, content_mean, content_isqrt, style_mean, style_sqrt, mix,
+                             style_regional ? style_count_or_null : nullptr, out, n, c, m, regions, styles, mix_n,
+                             style_regional ? 1 : 0, (float)alpha, wsp + perm_ws(n, m) + al256((int64_t)4 * n * regions),
+                             st);
+}
+
+long long ast_wct_regions_workspace_bytes(int n, int c, int hc, int wc, int regions, int styles, int hs, int ws,
+                                          int style_regional) {
+  const int e = regions_shape(n, c, hc, wc, regions, styles, hs, ws, style_regional, 1);
+  if (e) return e;
+  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws;
+  const int b = n * regions + styles * (style_regional ? regions : 1);
+  const int64_t spart = style_regional ? region_part_ws(styles, c, ms, regions) : cov_ws(styles, c, ms);
+  const int64_t part = region_part_ws(n, c, mc, regions) > spart ? region_part_ws(n, c, mc, regions) : spart;
+  return al256((int64_t)4 * b * c) + 3 * al256((int64_t)4 * b * c * c) + perm_ws(n, mc) +
+         al256((int64_t)4 * n * regions) + perm_ws(styles, ms) + al256((int64_t)4 * styles * regions) +
+         max3(part, sqrt_ws(b, c), region_mix_ws(n, c, regions));
+}
+
+int ast_wct_regions_f32(const float* content, const unsigned char* labels, const float* styles,
+                        const unsigned char* style_labels_or_null, const float* mix, float* out, int n, int c, int hc,
+                        int wc, int regions, int s, int hs, int ws, int mix_n, double alpha, float eps_rel, int iters,
+                        void* workspace, long long workspace_bytes, void* stream) {
+  if (!content || !labels || !styles || !mix || !out || !workspace) return AST_E_NULLPTR;
+  const int reg = style_labels_or_null ? 1 : 0;
+  int e = regions_shape(n, c, hc, wc, regions, s, hs, ws, reg, mix_n);
+  if (e) return e;
+  if (!eps_ok(eps_rel) || iters < 0) return AST_E_UNSUPPORTED;
+  if (workspace_bytes < ast_wct_regions_workspace_bytes(n, c, hc, wc, regions, s, hs, ws, reg)) return AST_E_SHAPE;
+  if (iters == 0) iters = default_iters(c, eps_rel);
+  hipStream_t st = (hipStream_t)stream;
+  // [mean | cov | sqrt | isqrt | content perm, counts | style perm, counts | scratch]: the n * regions
+  // content matrices first, then the styles'; the scratch is the covariance partials, then the
+  // iteration's buffers, then the apply stage's: stream order keeps them apart
+  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws, cc = (int64_t)c * c;
+  const int nk = n * regions, b = nk + s * (reg ? regions : 1);
+  const int64_t mb = al256((int64_t)4 * b * cc);
+  unsigned char* w = (unsigned char*)workspace;
+  float* mean = (float*)w;
+  float* cov = (float*)(w + al256((int64_t)4 * b * c));
+  float* root = (float*)((unsigned char*)cov + mb);
+  float* iroot = (float*)((unsigned char*)root + mb);
+  int* cperm = (int*)((unsigned char*)iroot + mb);
+  int* ccount = (int*)((unsigned char*)cperm + perm_ws(n, mc));
+  int* sperm = (int*)((unsigned char*)ccount + al256((int64_t)4 * nk));
+  int* scount = (int*)((unsigned char*)sperm + perm_ws(s, ms));
+  unsigned char* scratch = (unsigned char*)scount + al256((int64_t)4 * s * regions);
+  e = bin_launch(labels, cperm, ccount, n, mc, regions, st);
+  if (e) return e;
+  e = region_cov_launch(content, cperm, ccount, mean, cov, n, c, mc, regions, eps_rel, (float*)scratch, st);
+  if (e) return e;
+  float* smean = mean + (int64_t)nk * c;
+  if (reg) {
+    e = bin_launch(style_labels_or_null, sperm, scount, s, ms, regions, st);
+    if (e) return e;
+    e = region_cov_launch(styles, sperm, scount, smean, cov + nk * cc, s, c, ms, regions, eps_rel, (float*)scratch, st);
+  } else {
+    e = cov_launch(styles, smean, cov + nk * cc, s, c, ms, eps_rel, (float*)scratch, st);
+  }
+  if (e) return e;
+  e = sqrt_launch(cov, root, iroot, b, c, iters, scratch, st);
+  if (e) return e;
+  return region_apply_launch(content, cperm, ccount, mean, iroot, smean, root + nk * cc, mix, reg ? scount : nullptr, out,
+                             n, c, mc, regions, s, mix_n, reg, (float)alpha, scratch, st);
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@ adain_regions           -- (regional multi-style AdaIN)              --
 efdm                    -- (exact feature distribution matching)     d content = grad (straight-through)
 plane_sort              -- (segmented totalOrder sort of planes)     --
 wct                     -- (whitening and colouring transform)       raises NotImplementedError
+wct_regions             -- (WCT per region, mix of a style bank)     raises NotImplementedError
 style_swap              -- (patch-matching style swap)               raises NotImplementedError
 style_swap_guided       -- (class-guided style swap over a bank)     raises NotImplementedError
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
@@ -745,6 +746,27 @@ def _wct_backward(ctx, g):
 register_autograd("ast_hip::wct", _wct_backward)
 
 
+@custom_op("ast_hip::wct_regions", mutates_args=())
+def wct_regions(content: Tensor, labels: Tensor, styles: Tensor, mix: Tensor, style_labels: Optional[Tensor],
+                alpha: float, eps_rel: float, iters: int) -> Tensor:
+    """WCT per region of a uint8 label map towards a per-region mix [N or 1, K, S] of a bank of styles."""
+    return ops.wct_regions(content, labels, styles, mix, style_labels=style_labels, alpha=alpha, eps_rel=eps_rel,
+                           iters=iters)
+
+
+@register_fake("ast_hip::wct_regions")
+def _(content, labels, styles, mix, style_labels, alpha, eps_rel, iters):
+    return torch.empty_like(content)
+
+
+def _wct_regions_backward(ctx, g):
+    raise NotImplementedError("ast_hip::wct_regions has no backward: the whitening and colouring transform is "
+                              "inference-only")
+
+
+register_autograd("ast_hip::wct_regions", _wct_regions_backward)
+
+
 # ------------------------------------------------------------------------------------------------
 # Style swap (csrc/swap.hip; inference only)
 # ------------------------------------------------------------------------------------------------
@@ -789,5 +811,5 @@ register_autograd("ast_hip::style_swap_guided", _style_swap_guided_backward)
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "style_swap",
+                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "wct_regions", "style_swap",
                   "style_swap_guided"]

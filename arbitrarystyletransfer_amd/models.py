@@ -447,7 +447,8 @@ class AdaINStyleTransfer(nn.Module):
     inference-only (the forward raises NotImplementedError when a gradient is asked for).
     `stylize_swap` stylises by style swap (patch matching on the relu4_1 maps) with the same
     encoder and decoder, whatever the transform; `stylize_swap_regions` is its guided form over a
-    bank of styles, steered by the label maps of `stylize_regions`.
+    bank of styles, steered by the label maps of `stylize_regions`. `stylize_regions_wct` is
+    `stylize_regions` with WCT per region (ops.wct_regions), also whatever the transform.
     """
 
     TRANSFORMS = ("adain", "efdm", "wct")
@@ -628,6 +629,47 @@ class AdaINStyleTransfer(nn.Module):
                 mix[:, r, r * s:(r + 1) * s] = w[:, r]
         t = ops.adain_regions(f_c, lab, mean, std, mix.float().to(f_c.device), alpha=alpha,
                               swap_style_stats=not self.adain.canonical)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
+
+    def stylize_regions_wct(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
+                            style_labels=None, preserve_color: bool = False, eps_rel: float = ops.WCT_EPS_REL,
+                            iters: int = 0):
+        """stylize_regions with the whitening and colouring transform (ops.wct_regions on the relu4_1
+        maps) in AdaIN's place: region k is whitened with its own covariance and coloured with the
+        weights[k]-mix of the styles' covariance roots and means (Li et al. 2017, section 4). Inference
+        only, whatever `transform` the model was built with.
+
+        content_img, style_imgs, labels, weights, style_labels, alpha and preserve_color as in
+        stylize_regions (labels=None: one region, plain style interpolation; weights=None: region k
+        takes style k, or equal weights when labels is None). With style_labels region k takes the
+        statistics of each style's own region k; where a style of non-zero weight has fewer than 2
+        such pixels, the region keeps the content's features. eps_rel and iters as WCT."""
+        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("stylize_regions_wct is inference-only; run it under torch.no_grad()")
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError("stylize_regions_wct needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
+        if s > ops.MAX_STYLE_ROWS:
+            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
+        w = region_weights(weights, n, s, single_region=labels is None)
+        f_c = self.encoder(content_img)[0]
+        f_s = self.encoder(style_imgs)[0]
+        if labels is None:
+            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
+        else:
+            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(f_c.device)
+        sl = None
+        if style_labels is not None:
+            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(f_c.device)
+        mix = w.float().to(f_c.device)
+        if _compiling():
+            t = _ops().wct_regions(f_c, lab, f_s, mix, sl, float(alpha), float(eps_rel), int(iters))
+        else:
+            t = ops.wct_regions(f_c, lab, f_s, mix, style_labels=sl, alpha=alpha, eps_rel=eps_rel, iters=iters)
         out = self.decoder(t)
         if preserve_color:
             return _luma_transfer(out, content_img)

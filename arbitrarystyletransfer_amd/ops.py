@@ -527,6 +527,115 @@ def wct(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, eps_rel:
     return out
 
 
+# Regional WCT (csrc/wct.hip): per-region whitening and colouring towards a per-region mix of styles
+
+def _region_mix(mix, n: int, s: int, device, what: str):
+    """mix [K, S], [1, K, S] or [N, K, S] on the device -> (mix [1 or N, K, S], K)."""
+    mix = _dev(mix, "mix")
+    if mix.dim() == 2:
+        mix = mix.unsqueeze(0)
+    if (mix.dim() != 3 or mix.shape[0] not in (1, n) or not 1 <= mix.shape[1] <= MAX_REGIONS or mix.shape[2] != s
+            or mix.device != device):
+        raise HipOpError(f"{what}: mix must be [N={n} or 1, K <= {MAX_REGIONS}, S={s}] on {device}, got "
+                         f"{tuple(mix.shape)} on {mix.device}")
+    return mix, int(mix.shape[1])
+
+
+def wct_region_cov(x: torch.Tensor, labels: torch.Tensor, regions: int, eps_rel: float = WCT_EPS_REL):
+    """(mean [N, K, C], cov [N, K, C, C], count [N, K] int32) of x [N, C, H, W] under labels [N, H, W]
+    (uint8; a label >= regions belongs to no region): wct_cov of each region's pixels taken in
+    ascending pixel index, bit for bit. A region of fewer than 2 pixels has mean 0 and cov = I."""
+    regions = _regions(regions)
+    x, labels, n, c, h, w = _map_and_labels(x, labels, "x")
+    L = lib()
+    nbytes = int(L.ast_wct_region_cov_workspace_bytes(n, c, h, w, regions))
+    wsb = _ws_bytes(nbytes, "wct_region_cov workspace", x.device)
+    mean = torch.empty((n, regions, c), device=x.device, dtype=torch.float32)
+    cov = torch.empty((n, regions, c, c), device=x.device, dtype=torch.float32)
+    count = torch.empty((n, regions), device=x.device, dtype=torch.int32)
+    check(_timed(f"wct_region_cov {c}ch {h}x{w} K{regions}", n * c * (c + 1) * h * w, x.device,
+                 lambda: L.ast_wct_region_cov_f32(ptr(x), ptr(labels), ptr(mean), ptr(cov), ptr(count), n, c, h, w,
+                                                  regions, float(eps_rel), ptr(wsb), nbytes, stream_ptr(x.device))),
+          "wct_region_cov")
+    return mean, cov, count
+
+
+def wct_region_apply(content: torch.Tensor, labels: torch.Tensor, content_mean: torch.Tensor,
+                     content_isqrt: torch.Tensor, style_mean: torch.Tensor, style_sqrt: torch.Tensor, mix: torch.Tensor,
+                     style_count: torch.Tensor = None, alpha: float = 1.0):
+    """The apply stage of wct_regions from its parts: content_mean [N, K, C] and content_isqrt
+    [N, K, C, C] (wct_region_cov, wct_sqrt); style_mean [S, C] and style_sqrt [S, C, C] of whole style
+    maps, or [S, K, C] and [S, K, C, C] of their regions with style_count [S, K] (int32; None: every
+    style region counts as valid); mix as wct_regions."""
+    content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
+    sm, sr = _dev(style_mean, "style_mean"), _dev(style_sqrt, "style_sqrt")
+    if sm.dim() not in (2, 3) or sm.numel() == 0:
+        raise HipOpError(f"style_mean must be [S, C] or [S, K, C], got {tuple(sm.shape)}")
+    s, regional = int(sm.shape[0]), sm.dim() == 3
+    mix, k = _region_mix(mix, n, s, content.device, "wct_region_apply")
+    cm, ci = _dev(content_mean, "content_mean"), _dev(content_isqrt, "content_isqrt")
+    lead = (s, k) if regional else (s,)
+    if (tuple(cm.shape) != (n, k, c) or tuple(ci.shape) != (n, k, c, c) or tuple(sm.shape) != lead + (c,)
+            or tuple(sr.shape) != lead + (c, c)):
+        raise HipOpError(f"wct_region_apply needs content statistics [{n}, {k}, {c}(, {c})] and style statistics "
+                         f"{list(lead)} + [{c}(, {c})], got {tuple(cm.shape)}, {tuple(ci.shape)}, {tuple(sm.shape)}, "
+                         f"{tuple(sr.shape)}")
+    if any(t.device != content.device for t in (cm, ci, sm, sr)):
+        raise HipOpError(f"wct_region_apply: every tensor must be on {content.device}")
+    sc = None
+    if style_count is not None:
+        sc = _dev_typed(style_count, "style_count", torch.int32)
+        if not regional or tuple(sc.shape) != (s, k) or sc.device != content.device:
+            raise HipOpError(f"style_count goes with regional style statistics and must be [S={s}, K={k}] int32 on "
+                             f"{content.device}, got {tuple(sc.shape)}")
+    L = lib()
+    nbytes = int(L.ast_wct_region_apply_workspace_bytes(n, c, h, w, k))
+    wsb = _ws_bytes(nbytes, "wct_region_apply workspace", content.device)
+    out = torch.empty_like(content)
+    check(_timed(f"wct_region_apply {c}ch {h}x{w} K{k}", 2 * n * c * c * (h * w + k * c), content.device,
+                 lambda: L.ast_wct_region_apply_f32(
+                     ptr(content), ptr(labels), ptr(cm), ptr(ci), ptr(sm), ptr(sr), ptr(mix), ptr(sc), ptr(out), n, c, h,
+                     w, k, s, int(mix.shape[0]), 1 if regional else 0, float(alpha), ptr(wsb), nbytes,
+                     stream_ptr(content.device))), "wct_region_apply")
+    return out
+
+
+def wct_regions(content: torch.Tensor, labels: torch.Tensor, styles: torch.Tensor, mix: torch.Tensor,
+                style_labels: torch.Tensor = None, alpha: float = 1.0, eps_rel: float = WCT_EPS_REL, iters: int = 0):
+    """Regional WCT (Li et al., NeurIPS 2017, section 4): region k of sample n (the pixels with
+    labels[n] == k) is whitened with its own mean and covariance and coloured with the mix
+    sum_s mix[n, k, s] * (cov_s^(1/2), mu_s) of the S styles [S, C, Hs, Ws] (shared by the batch); with
+    style_labels [S, Hs, Ws] the statistics are those of each style's own region k. Pixels labelled
+    >= K, regions of fewer than 2 pixels and regions whose class a used style lacks pass through bit
+    for bit. mix is [K, S], [1, K, S] or [N, K, S] on the device, rows summing to 1; a style of weight
+    exactly 0 is never read. alpha, eps_rel and iters as wct."""
+    content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
+    styles = _dev(styles, "styles")
+    if styles.dim() != 4 or styles.numel() == 0 or styles.shape[1] != c or styles.device != content.device:
+        raise HipOpError(f"wct_regions needs a non-empty style bank [S, C={c}, Hs, Ws] on {content.device}, got "
+                         f"{tuple(styles.shape)} on {styles.device}")
+    s, hs, ws = int(styles.shape[0]), int(styles.shape[2]), int(styles.shape[3])
+    mix, k = _region_mix(mix, n, s, content.device, "wct_regions")
+    if style_labels is not None:
+        style_labels = _labels(style_labels, "style_labels")
+        if tuple(style_labels.shape) != (s, hs, ws) or style_labels.device != content.device:
+            raise HipOpError(f"style_labels must be [S, Hs, Ws] = {(s, hs, ws)} on {content.device}, got "
+                             f"{tuple(style_labels.shape)} on {style_labels.device}")
+    L = lib()
+    nbytes = int(L.ast_wct_regions_workspace_bytes(n, c, h, w, k, s, hs, ws, 0 if style_labels is None else 1))
+    wsb = _ws_bytes(nbytes, "wct_regions workspace", content.device)
+    out = torch.empty_like(content)
+    # the stages' counts: both covariances, the roots of all the matrices, T and the apply GEMM
+    b = n * k + s * (1 if style_labels is None else k)
+    it = int(iters) or (wct_default_iters(c, eps_rel) if c <= WCT_MAX_C and 1e-4 <= eps_rel <= 1 else 0)
+    flops = c * (c + 1) * (n * h * w + s * hs * ws) + 6 * b * c ** 3 * max(it, 0) + 2 * n * c * c * (h * w + k * c)
+    check(_timed(f"wct_regions {c}ch {h}x{w} K{k} S{s}", flops, content.device, lambda: L.ast_wct_regions_f32(
+        ptr(content), ptr(labels), ptr(styles), ptr(style_labels), ptr(mix), ptr(out), n, c, h, w, k, s, hs, ws,
+        int(mix.shape[0]), float(alpha), float(eps_rel), int(iters), ptr(wsb), nbytes, stream_ptr(content.device))),
+        "wct_regions")
+    return out
+
+
 # Style swap (csrc/swap.hip): the limits of ast_hip.h
 SWAP_MAX_C = 1024
 

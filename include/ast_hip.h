@@ -258,6 +258,74 @@ int ast_wct_f32(const float* content, const float* style, float* out, int n, int
                 int iters /* 0 = the default above */, void* workspace, long long workspace_bytes,
                 void* stream);
 
+/* Regional WCT (Li et al. 2017, section 4: spatial control and style interpolation; csrc/wct.hip):
+ * the transform above per region of a label map, towards a per-region mix of a bank of styles.
+ * Inputs: content x [n, c, h, w] fp32; labels uint8 [n, h, w], M = h*w <= 2^24, K = regions in
+ * 1..AST_MAX_REGIONS: label k < K puts the pixel in region k, any label >= K (255 by convention)
+ * passes it through and keeps it out of every statistic. Styles s [S, c, hs, ws] shared by the batch,
+ * S in 1..AST_MAX_STYLE_ROWS, optionally with style_labels uint8 [S, hs, ws]. mix fp32 [n or 1, K, S]
+ * on the device, non-negative, rows summing to 1 (the caller normalises). c <= 1024 and
+ * n K + S (K with style labels, else 1) <= 32767.
+ * Region statistics: for region k of sample b take the M_k pixels labelled k in ascending pixel
+ * index as a c x M_k map; mu and Sigma are exactly those of ast_wct_cov_f32 on that map, bit for bit
+ * (mean x0 + sum(x - x0) / M_k with x0 the region's first pixel, two-pass centring, / (M_k - 1), the
+ * ridge eps_rel * max(tr / c, 1e-20), Sigma symmetric in bits). A region with M_k < 2 is invalid: its
+ * Sigma is stored as the identity and its mean as 0, so the batched roots stay finite. The style side
+ * is ast_wct_cov_f32 of the whole style map or, with style_labels, the regional statistics of style
+ * s's own region k.
+ * Transform of region k: U_k = the styles with mix[b, k, s] != 0; C_k = sum_{s in U_k} w_s Sigma_s^(1/2)
+ * and m_k = sum_{s in U_k} w_s mu_s in ascending s, the first used term the product w Y and the later
+ * ones fmaf(w, Y, acc), so a one-hot row reproduces Sigma_s^(1/2) and mu_s in bits; a style of weight
+ * exactly 0 is never read and may hold NaN. T_k = C_k Sigma_(c,k)^(-1/2), t = T_k (x - mu_(c,k)) + m_k,
+ * out = alpha t + (1 - alpha) x on the region's pixels: the paper's interpolation, a blend of the
+ * transformed features, as one GEMM per region.
+ * Pass-through, out = x bit for bit whatever alpha: where label >= K; in an invalid content region;
+ * in a region one of whose used styles has an invalid region k (style_labels: the class is absent
+ * from the bank); in a region whose weights are all 0.
+ * Roots: ast_wct_sqrt_f32, same eps_rel range and iters default, all matrices as one batch.
+ * The pixels are binned by region once (a permutation ordered by (min(label, K), pixel index) and K
+ * counts per sample) and every product reads its pixel axis through it: the MFMA work is that of the
+ * unmasked transform whatever K. No atomics, no host synchronisation, no allocation; no launch
+ * parameter depends on the contents of a label map, so a captured graph replays with other labels.
+ * A non-finite value stays inside its own region of its own sample.
+ * Workspaces are device memory, 256-byte aligned, of at least the matching *_workspace_bytes query.
+ * AST_E_NULLPTR: a null pointer (but the optional ones). AST_E_SHAPE: a size <= 0, a plane over 2^24
+ * pixels, a style plane below 2 pixels without style labels, regions or S out of range, a mix batch
+ * outside {1, n}, too many matrices, a short workspace. AST_E_UNSUPPORTED: eps_rel outside [1e-4, 1],
+ * c > 1024, iters < 0. The queries return the same negative codes. All checks run before the first
+ * launch. */
+
+/* mean [n, K, c], cov [n, K, c, c] (ridge included; the identity and 0 for an invalid region) and
+ * count [n, K] (int32) of x under labels. */
+long long ast_wct_region_cov_workspace_bytes(int n, int c, int h, int w, int regions);
+int ast_wct_region_cov_f32(const float* x, const unsigned char* labels, float* mean, float* cov,
+                           int* count, int n, int c, int h, int w, int regions, float eps_rel,
+                           void* workspace, long long workspace_bytes, void* stream);
+
+/* out from the parts: content_mean [n, K, c], content_isqrt [n, K, c, c]; style_mean [S, c] and
+ * style_sqrt [S, c, c] or, with style_regional != 0, [S, K, c] and [S, K, c, c] with their counts
+ * style_count_or_null [S, K] (NULL: every style region is valid; ignored when style_regional == 0);
+ * mix [mix_n, K, S] with mix_n == 1 or n. The content is binned again here; C_k, m_k and T_k take
+ * the workspace and t is never stored. */
+long long ast_wct_region_apply_workspace_bytes(int n, int c, int h, int w, int regions);
+int ast_wct_region_apply_f32(const float* content, const unsigned char* labels,
+                             const float* content_mean, const float* content_isqrt,
+                             const float* style_mean, const float* style_sqrt, const float* mix,
+                             const int* style_count_or_null, float* out, int n, int c, int h, int w,
+                             int regions, int styles, int mix_n, int style_regional, double alpha,
+                             void* workspace, long long workspace_bytes, void* stream);
+
+/* The whole op: exactly ast_wct_region_cov_f32 of the content, ast_wct_cov_f32 (or, with style
+ * labels, ast_wct_region_cov_f32) of the styles, ast_wct_sqrt_f32 of all the matrices as one batch
+ * (content regions first) and ast_wct_region_apply_f32, bit for bit. */
+long long ast_wct_regions_workspace_bytes(int n, int c, int hc, int wc, int regions, int styles,
+                                          int hs, int ws, int style_regional);
+int ast_wct_regions_f32(const float* content, const unsigned char* labels, const float* styles,
+                        const unsigned char* style_labels_or_null, const float* mix, float* out,
+                        int n, int c, int hc, int wc, int regions, int styles_count, int hs, int ws,
+                        int mix_n, double alpha, float eps_rel, int iters /* 0 = the default above */,
+                        void* workspace, long long workspace_bytes, void* stream);
+
 /* Style swap (Chen & Schmidt 2016; the style decorator of Avatar-Net, Sheng et al. CVPR 2018, when the
  * keys are normalised features; csrc/swap.hip; an extension, no reference counterpart): every 3x3
  * patch of the content map is replaced by the most similar patch of the style map and the overlaps
