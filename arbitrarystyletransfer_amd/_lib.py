@@ -33,6 +33,9 @@ SIGNATURES = {
     "ast_conv3x3_up2c_numel": (ctypes.c_size_t, [_i, _i]),
     "ast_conv3x3_pack_up2c_f32": (_i, [_p, _p, _i, _i, _p]),
     "ast_conv3x3_up2c_fwd_f32": (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ast_conv3x3_up2c_fwd_f32_cfg": (_i, [_i, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ast_conv3x3_up2c_variant": (_i, [_i, _i, _i, _i, _i]),
+    "ast_conv3x3_up2c_occupancy": (_i, [_i]),
     "ast_channel_stats_f32": (_i, [_p, _p, _p, _ll, _ll, _i, ctypes.c_float, _p]),
     "ast_adain_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, ctypes.c_double, _i, _p]),
     "ast_plane_normalize_f32": (_i, [_p, _p, _p, _p, _ll, _ll, _p]),

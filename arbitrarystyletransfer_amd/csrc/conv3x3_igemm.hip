@@ -737,7 +737,10 @@ __global__ __launch_bounds__(WM * 64, OCC) void conv3x3_x3_kernel(ConvArgs a) {
 
 #if X3_STAMP
   unsigned st0 = 0, st1 = 0, st2 = 0;
-  X3_ST(0);
+  {
+    const int lane = threadIdx.x & 63;  // the block loop declares its own
+    X3_ST(0);
+  }
 #endif
   static_assert(!PER || M16, "persistent form of the M16 kernel only");
   const int ntl = a.tiles_x * a.tiles_y * a.N, ngr = (a.Cout + BN - 1) / BN;
@@ -1245,29 +1248,40 @@ __global__ void pack_up2c_kernel(const float* __restrict__ wp, bf16* __restrict_
   }
 }
 
-template <int WM>
+// SLABS = 2: the 8-wave form above. SLABS = 1 (with WM = 4: 16 x 32 output pixels, a 10 x 18 source
+// tile, 18 KiB A tile + one 48-KiB slab under the 72 KiB of the epilogue regions): two workgroups per
+// CU, so one's prologue, barrier windows, slab landing and epilogue run under the other's MFMAs. The
+// single buffer is refilled between the chunk's two barriers.
+template <int WM, int SLABS = 2>
 struct Up2cCfg {
   using X = X3Cfg<WM, 4, 1, 2>;  // 4 output rows per wave, 32 channels: tile, gather and epilogue sizes
+  static_assert(SLABS == 1 || SLABS == 2, "");
+  static constexpr int OCC = SLABS == 1 ? 2 : 1;  // workgroups per CU the form is sized for
   static_assert(X::BN == kUp2cBN && X::TH == 4 * WM, "");
   static constexpr int B_ROWS = 3 * kUp2cTaps * 2;  // (plane, phase-tap, h)
   static constexpr int B_PLANE = kUp2cTaps * 2 * kUp2cBN;
   static constexpr int B_UNITS = B_ROWS * kUp2cBN;
-  static constexpr int LDS_TILES = (X::A_UNITS + 2 * B_UNITS) * 16;
+  static constexpr int LDS_TILES = (X::A_UNITS + SLABS * B_UNITS) * 16;
   static constexpr int LDS_BYTES = LDS_TILES > X::LDS_EPI ? LDS_TILES : X::LDS_EPI;
 };
 
-template <int WM>
-__global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, const u32x4* __restrict__ wc) {
-  using U = Up2cCfg<WM>;
+template <int WM, int SLABS = 2>
+__global__ __launch_bounds__(WM * 64, SLABS == 1 ? 2 : 1) void conv3x3_up2c_kernel(ConvArgs a, const u32x4* __restrict__ wc) {
+  using U = Up2cCfg<WM, SLABS>;
+  static_assert(U::OCC == (SLABS == 1 ? 2 : 1), "");
   using C = typename U::X;
   constexpr int NT = C::NT, TH = C::TH, BN = kUp2cBN, SR = C::SR, SC = C::SC, A_PLANE = C::A_PLANE;
   constexpr int HS = C::HS, A_ITEMS = C::A_ITEMS, A_T = C::A_T;
   constexpr int B_UNITS = U::B_UNITS, B_PLANE = U::B_PLANE;
   extern __shared__ __attribute__((aligned(16))) u32x4 x3_smem[];
   u32x4* As = x3_smem;
-  u32x4* Bs = x3_smem + C::A_UNITS;  // [2][plane][phase-tap][h][BN]
+  u32x4* Bs = x3_smem + C::A_UNITS;  // [SLABS][plane][phase-tap][h][BN]
 
   const int tid = threadIdx.x, wm = tid >> 6, lane = tid & 63;
+#if X3_STAMP
+  unsigned st0 = 0, st1 = 0, st2 = 0;
+  X3_ST(0);
+#endif
   const int ntl = a.tiles_x * a.tiles_y * a.N, ngr = (a.Cout + BN - 1) / BN;
   int t, grp;
   if (!decode_block(blockIdx.x, ntl, ngr, t, grp)) return;
@@ -1316,7 +1330,7 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
           ra[i][j] = xin[(int64_t)min(ci0 + 8 * g_h[i] + j, a.Cin - 1) * plane_in + g_pix[i]];          \
     }                                                                                                   \
   }
-  // the whole slab of chunk KC (48 lane-linear 1-KiB pieces, 6 per wave) into buffer KC & 1
+  // the whole slab of chunk KC (48 lane-linear 1-KiB pieces, 48 / WM per wave) into buffer KC & (SLABS - 1)
   static_assert(B_UNITS % (64 * WM) == 0, "whole 1-KiB pieces, the same count per wave");
 #define UP2C_DMA(KC)                                                                                    \
   _Pragma("unroll") for (int i = 0; i < B_UNITS / 64 / WM; ++i) {                                       \
@@ -1324,7 +1338,7 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
     const int u = piece * 64 + lane, row = u / BN, j = u - row * BN;                                    \
     const u32x4* src = wc + (int64_t)(KC) * chunk_units + (int64_t)row * a.cout_pad + n0 + j;           \
     __builtin_amdgcn_global_load_lds((const void*)src,                                                  \
-                                     (__attribute__((address_space(3))) void*)(Bs + ((KC) & 1) * B_UNITS + piece * 64), \
+                                     (__attribute__((address_space(3))) void*)(Bs + ((KC) & (SLABS - 1)) * B_UNITS + piece * 64), \
                                      16, 0, 0);                                                         \
   }
 #define UP2C_SPLIT_A(KC)                                                                                \
@@ -1361,12 +1375,14 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
   UP2C_WRITE_A;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the slab has landed
   __syncthreads();
+  X3_ST(1);
   static_assert(A_T < kUp2cTaps - 1, "one gather item per step, then the slab DMA");
   for (int kc = 0; kc < nch; ++kc) {
     __builtin_amdgcn_sched_barrier(0);
+    X3_ST(2 + 4 * kc);
     bf16x8 gb[2][3][2];  // B fragments (g1, g2, g3) of a phase-tap, by step parity
     bf16x8 fa[2][2][2];  // A fragments (f1, f2) of the two source rows, by position parity
-    const u32x4* __restrict__ bs = Bs + (kc & 1) * B_UNITS;
+    const u32x4* __restrict__ bs = Bs + (kc & (SLABS - 1)) * B_UNITS;
     const u32x4* __restrict__ bp1 = bs;                                           // hi
     const u32x4* __restrict__ bp2 = bs + (g16 < 2 ? B_PLANE : 0);                 // mid | hi
     const u32x4* __restrict__ bp3 = bs + (g16 < 2 ? 2 * B_PLANE : B_PLANE);       // lo | mid
@@ -1394,7 +1410,7 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
         UP2C_LOAD_A(kc + 1, st, st + 1)
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (st == A_T && kc + 1 < nch) {
+      if (SLABS == 2 && st == A_T && kc + 1 < nch) {
         __builtin_amdgcn_sched_barrier(0);
         UP2C_DMA(kc + 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -1438,12 +1454,28 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
 #undef UP2C_READ_A
 #undef UP2C_READ_B
     __builtin_amdgcn_sched_barrier(0);
+    X3_ST(3 + 4 * kc);
     if (kc + 1 < nch) {
       UP2C_SPLIT_A(kc + 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next slab has landed
-      __syncthreads();  // every wave is done reading this chunk's A tile
-      UP2C_WRITE_A;
-      __syncthreads();
+      if constexpr (SLABS == 2) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next slab has landed
+        __syncthreads();  // every wave is done reading this chunk's A tile
+        X3_ST(4 + 4 * kc);
+        UP2C_WRITE_A;
+        __syncthreads();
+      } else {
+        // one slab buffer: it is refilled once every wave is done reading it. Nothing orders another
+        // wave's ds_read behind a pending LDS-DMA but the issuing wave's vmcnt wait and a barrier
+        // after it: the landing is exposed here, for the CU's other workgroup to run under.
+        __syncthreads();  // every wave is done reading this chunk's A tile and slab (no DMA pending)
+        X3_ST(4 + 4 * kc);
+        UP2C_DMA(kc + 1);
+        UP2C_WRITE_A;
+        X3_ST(120 + kc);  // SLABS = 1 only: slab DMA issued and A tile written; to 5 + 4 kc = the exposed landing
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next slab has landed
+        __syncthreads();
+      }
+      X3_ST(5 + 4 * kc);
     }
   }
 #undef UP2C_LOAD_A
@@ -1454,6 +1486,7 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
   // staged epilogue: lane (l16, g16) holds source pixels 4 g16 + k of channel 16 q + l16 for both
   // px, i.e. output pixels 8 g16 .. + 7 once interleaved: two float4 per (output row, channel)
   __syncthreads();  // every wave is done reading the last chunk's tiles
+  X3_ST(2 + 4 * nch);
   float* region = reinterpret_cast<float*>(x3_smem) + wm * 32 * 4 * 36;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -1472,6 +1505,24 @@ __global__ __launch_bounds__(WM * 64, 1) void conv3x3_up2c_kernel(ConvArgs a, co
   __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
   __builtin_amdgcn_wave_barrier();
   store_region<4>(a, region, n, x0, y0, 4 * wm, n0, lane);
+#if X3_STAMP
+  __builtin_amdgcn_s_waitcnt(0);  // the epilogue's stores have left (vmcnt 0)
+  X3_ST(3 + 4 * nch);
+  if (blockIdx.x < kX3StampWgs) {
+    unsigned* rec = x3_stamp_buf + ((size_t)blockIdx.x * 16 + wm) * kX3StampRec;
+    rec[lane] = st0;
+    rec[64 + lane] = st1;
+    rec[128 + lane] = st2;
+    if (lane == 0) {
+      rec[192] = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID: wave, SIMD, CU, SE
+      rec[193] = __builtin_amdgcn_s_getreg(20 | (3 << 11));   // HW_REG_XCC_ID
+      rec[194] = blockIdx.x;
+      rec[195] = nch;
+      rec[196] = 0x57a3u;
+      rec[197] = WM * 16 + SLABS;  // the up2c form (0 in conv3x3_x3_kernel's records)
+    }
+  }
+#endif
 }
 
 // Persistent form of the M16 split-bf16 kernel (round 4). One workgroup per CU
@@ -2370,24 +2421,61 @@ int launch_x3(const ConvArgs& a, hipStream_t s, int up) {
 
 // collapsed upsampled conv (conv3x3_up2c_kernel): 32x32 px x 32 ch tiles, 8 waves; not in kConfigs --
 // it reads the collapsed slab, a buffer of its own (ast_conv3x3_up2c_fwd_f32)
-int launch_up2c(const ConvArgs& a0, const float* w_up2c, hipStream_t s) {
-  using U = Up2cCfg<8>;
+constexpr int kUp2cFourWaveMaxChunks = 16;  // K chunks per block up to which a full launch takes the 4-wave form
+
+template <int WM, int SLABS>
+const void* up2c_kernel_ptr() {  // the kernel with its dynamic-LDS attribute set (once per instantiation)
+  using U = Up2cCfg<WM, SLABS>;
+  static_assert(U::LDS_BYTES * U::OCC <= 160 * 1024, "LDS per CU");
+  static const void* kern = [] {
+    const void* k = (const void*)conv3x3_up2c_kernel<WM, SLABS>;
+    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, U::LDS_BYTES);
+    return k;
+  }();
+  return kern;
+}
+
+template <int WM, int SLABS>
+int64_t up2c_blocks(const ConvArgs& a) {
+  const int64_t ntiles = (int64_t)cdiv(a.W, TW) * cdiv(a.H, Up2cCfg<WM, SLABS>::X::TH) * a.N;
+  return (ntiles + 7) / 8 * 8 * cdiv(a.Cout, kUp2cBN);
+}
+
+template <int WM, int SLABS>
+int launch_up2c_one(const ConvArgs& a0, const float* w_up2c, hipStream_t s) {
+  using U = Up2cCfg<WM, SLABS>;
   ConvArgs a = a0;
   a.tiles_x = cdiv(a.W, TW);
   a.tiles_y = cdiv(a.H, U::X::TH);
-  const int64_t ntiles = (int64_t)a.tiles_x * a.tiles_y * a.N;
-  const int64_t nblk = (ntiles + 7) / 8 * 8 * cdiv(a.Cout, kUp2cBN);
+  const int64_t nblk = up2c_blocks<WM, SLABS>(a);
   if (nblk >= 0x7fffffff) return AST_E_SHAPE;
-  auto kern = conv3x3_up2c_kernel<8>;
-  constexpr int lds = U::LDS_BYTES;
-  static_assert(lds <= 160 * 1024, "LDS per CU");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(U::X::NT), lds, s, a, reinterpret_cast<const u32x4*>(w_up2c));
+  (void)up2c_kernel_ptr<WM, SLABS>();
+  hipLaunchKernelGGL((conv3x3_up2c_kernel<WM, SLABS>), dim3((unsigned)nblk), dim3(U::X::NT), U::LDS_BYTES, s, a,
+                     reinterpret_cast<const u32x4*>(w_up2c));
   return (int)hipGetLastError();
+}
+
+// The form auto takes (8: 8 waves, one workgroup per CU; 4: 4 waves, one slab buffer, two per CU).
+// AST_UP2C_TILE=8|4 (read once) forces one for A/B runs; the rule is the measured one of DESIGN.md §3.
+int up2c_auto_variant(const ConvArgs& a) {
+  static const int forced = [] {
+    const char* v = getenv("AST_UP2C_TILE");
+    const int t = v ? atoi(v) : 0;
+    return t == 4 || t == 8 ? t : 0;
+  }();
+  if (forced) return forced;
+  // measured (profiles/r08_up2c_*): a launch whose 8-wave workgroups do not fill the
+  // CUs runs on twice as many as 4-wave ones; a full launch gains most where prologue and epilogue
+  // weigh most (-18% at 4 chunks per block, -3% at 16 inside the decoder); past 16 nothing is measured
+  if (up2c_blocks<8, 2>(a) < cu_count()) return 4;
+  return cdiv(a.Cin, kX3K) <= kUp2cFourWaveMaxChunks ? 4 : 8;
+}
+
+int launch_up2c(const ConvArgs& a, const float* w_up2c, hipStream_t s, int variant) {
+  if (variant == 0) variant = up2c_auto_variant(a);
+  if (variant == 4) return launch_up2c_one<4, 1>(a, w_up2c, s);
+  if (variant == 8) return launch_up2c_one<8, 2>(a, w_up2c, s);
+  return AST_E_UNSUPPORTED;
 }
 
 struct CfgEntry {
@@ -2533,10 +2621,11 @@ int ast_conv3x3_pack_up2c_f32(const float* w_packed, float* w_up2c, int cout, in
   return (int)hipGetLastError();
 }
 
-int ast_conv3x3_up2c_fwd_f32(const float* x, const float* x2, int n2, const float* w_up2c, const float* bias,
-                             float* y_pre, float* y_act, int n, int cin, int h_in, int w_in, int cout, int upsample,
-                             int pad_mode, void* stream) {
+int ast_conv3x3_up2c_fwd_f32_cfg(int variant, const float* x, const float* x2, int n2, const float* w_up2c,
+                                 const float* bias, float* y_pre, float* y_act, int n, int cin, int h_in, int w_in,
+                                 int cout, int upsample, int pad_mode, void* stream) {
   if (!x || !w_up2c) return AST_E_NULLPTR;
+  if (variant != 0 && variant != 4 && variant != 8) return AST_E_UNSUPPORTED;
   if (n2 < 0 || (n2 > 0 && !x2)) return AST_E_NULLPTR;
   if (!y_pre && !y_act) return AST_E_NULLPTR;
   if (n <= 0 || cin <= 0 || h_in <= 0 || w_in <= 0 || cout <= 0) return AST_E_SHAPE;
@@ -2551,7 +2640,31 @@ int ast_conv3x3_up2c_fwd_f32(const float* x, const float* x2, int n2, const floa
   a.cin_pad = round_up(cin, kCinAlign);
   a.cout_pad = round_up(cout, kCoutAlign);
   a.reflect = 1;
-  return launch_up2c(a, w_up2c, (hipStream_t)stream);
+  return launch_up2c(a, w_up2c, (hipStream_t)stream, variant);
+}
+
+int ast_conv3x3_up2c_fwd_f32(const float* x, const float* x2, int n2, const float* w_up2c, const float* bias,
+                             float* y_pre, float* y_act, int n, int cin, int h_in, int w_in, int cout, int upsample,
+                             int pad_mode, void* stream) {
+  return ast_conv3x3_up2c_fwd_f32_cfg(0, x, x2, n2, w_up2c, bias, y_pre, y_act, n, cin, h_in, w_in, cout, upsample,
+                                      pad_mode, stream);
+}
+
+int ast_conv3x3_up2c_variant(int n, int cin, int h_in, int w_in, int cout) {
+  if (n <= 0 || cin <= 0 || h_in <= 0 || w_in <= 0 || cout <= 0) return AST_E_SHAPE;
+  ConvArgs a{};
+  a.N = n; a.Cin = cin; a.Cout = cout; a.H = 2 * h_in; a.W = 2 * w_in;
+  return up2c_auto_variant(a);
+}
+
+int ast_conv3x3_up2c_occupancy(int variant) {
+  int nb = 0;
+  hipError_t e = hipErrorInvalidValue;
+  if (variant == 4)
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, up2c_kernel_ptr<4, 1>(), Up2cCfg<4, 1>::X::NT, Up2cCfg<4, 1>::LDS_BYTES);
+  else if (variant == 8)
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, up2c_kernel_ptr<8, 2>(), Up2cCfg<8, 2>::X::NT, Up2cCfg<8, 2>::LDS_BYTES);
+  return e == hipSuccess ? nb : -1;
 }
 
 #if X3_STAMP

@@ -154,12 +154,13 @@ def pack_plan(n: int, w: int, pool: bool):
 def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, *, upsample: int = 1,
             pad_mode: str = "zeros", in_mean=None, in_std=None,
             want_pre: bool = False, want_act: bool = True, want_pool: bool = False, cfg: int = -1,
-            x2: torch.Tensor | None = None, _pack: bool = True, _flops=None):
+            x2: torch.Tensor | None = None, _pack: bool = True, _flops=None, _up2c_tile: int = 0):
     """Fused [Upsample x2] -> pad(1) -> Conv3x3 -> (+bias) -> {pre, ReLU, ReLU+MaxPool2x2}.
 
     x2 (optional): a second batch with x's C, H, W; outputs hold x's images then x2's (one
     launch for a content batch and a style batch, no concatenation copy).
     Returns (pre, act, pool) with None for outputs not requested.
+    _up2c_tile (tests): the collapsed kernel's form, 8 or 4 waves (0: the library's choice).
     """
     x = _dev(x, "x")
     if x.dim() != 4:
@@ -222,9 +223,11 @@ def conv3x3(x: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, *, upsampl
         return tuple(res)
     flops = _flops if _flops is not None else 2 * n * H * W * cout * cin * 9   # algorithmic (9 taps)
     tag = f"conv3x3 {cin}->{cout} {H}x{W} up{upsample} {pad_mode}"
+    if _up2c_tile and not up2c:
+        raise HipOpError("_up2c_tile: this call does not run the collapsed kernel")
     if up2c:
-        code = _timed(tag, flops, x.device, lambda: lib().ast_conv3x3_up2c_fwd_f32(
-            ptr(x), ptr(x2), n2, ptr(w_packed[base:]), ptr(bias), ptr(pre), ptr(act), n1, cin, h_in, w_in, cout,
+        code = _timed(tag, flops, x.device, lambda: lib().ast_conv3x3_up2c_fwd_f32_cfg(
+            _up2c_tile, ptr(x), ptr(x2), n2, ptr(w_packed[base:]), ptr(bias), ptr(pre), ptr(act), n1, cin, h_in, w_in, cout,
             upsample, PAD_MODES[pad_mode], stream_ptr(x.device)))
         check(code, "conv3x3 up2c")
         return pre, act, pool

@@ -103,6 +103,17 @@ int ast_conv3x3_up2c_fwd_f32(const float* x, const float* x2, int n2, const floa
                              const float* bias, float* y_pre, float* y_act,
                              int n, int cin, int h_in, int w_in, int cout,
                              int upsample, int pad_mode, void* stream);
+/* The same with the kernel form given: variant 8 = 8 waves, 32 x 32 output pixels, one workgroup
+ * per CU; 4 = 4 waves, 16 x 32 output pixels, one weight-slab buffer, two workgroups per CU; 0 =
+ * auto (what ast_conv3x3_up2c_fwd_f32 runs; AST_UP2C_TILE=8|4, read once, forces one). Both forms
+ * give the same bits. ast_conv3x3_up2c_variant: the form auto takes for a shape (n images in all).
+ * ast_conv3x3_up2c_occupancy: workgroups of a form that fit on one CU at its launch size (-1: error). */
+int ast_conv3x3_up2c_fwd_f32_cfg(int variant, const float* x, const float* x2, int n2, const float* w_up2c,
+                                 const float* bias, float* y_pre, float* y_act,
+                                 int n, int cin, int h_in, int w_in, int cout,
+                                 int upsample, int pad_mode, void* stream);
+int ast_conv3x3_up2c_variant(int n, int cin, int h_in, int w_in, int cout);
+int ast_conv3x3_up2c_occupancy(int variant);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-channel statistics and AdaIN.
