@@ -13,7 +13,7 @@ struct Cin3Args {
   float* y_act;
   const float* in_mean;  // ImageNet normalisation in the gather (VGG conv_1), or null
   const float* in_std;
-  // input-gradient epilogue of ast_conv3x3_dgrad_f32 on y_pre (ConvArgs e_* of conv3x3_igemm.hip)
+  // input-gradient epilogue of ast_conv3x3_dgrad_f32 on y_pre (ConvArgs e_* of conv_common.h)
   const float* e_mask;
   const float* e_add_pre;
   const float* e_add_post;

@@ -19,24 +19,18 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/ast_hip.h"
+#include "conv_common.h"
 #include "x3.h"
 #include "wgco3.h"
 #include "det.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
-
-template <int UP>
-__device__ __forceinline__ int src_index(int g, int n, int reflect) {
-  if (g >= 0 && g < n) return g;
-  if (!reflect) return -1;
-  if (UP == 2) return g < 0 ? 0 : n - 1;
-  int r = g < 0 ? -g : 2 * (n - 1) - g;
-  return r < 0 ? 0 : (r >= n ? n - 1 : r);
-}
+using ast_conv::cdiv;
+using ast_conv::f32x16;
+using ast_conv::relu_f;
+using ast_conv::round_up;
+using ast_conv::src_index;
 
 // wp[ci_pad][9][co_pad] layout of the forward pack, but for the transposed+flipped filter:
 // W'[o=ci][i=co][ky][kx] = W[co][ci][2-ky][2-kx] / (scale ? scale[ci] : 1)
@@ -306,7 +300,7 @@ __global__ void relu_mask_kernel(const float* __restrict__ g, const float* __res
 
 // Input-gradient epilogue outside the conv (configurations without it: ops.conv3x3_dgrad's fallback):
 // dx[p][r][c] = epi(up == 2 ? the 2x2 window sum of raw (row by row) : raw[p][r][c]) with
-// epi(v) = mask > 0 ? add_post + (v + add_pre) : add_post -- conv3x3_igemm.hip's dgrad_epi_one.
+// epi(v) = mask > 0 ? add_post + (v + add_pre) : add_post -- conv_common.h's dgrad_epi_one.
 __global__ void dgrad_finish_kernel(const float* __restrict__ raw, float* __restrict__ dx, const float* __restrict__ mask,
                                     const float* __restrict__ add_pre, const float* __restrict__ add_post,
                                     int64_t planes, int h, int w, int up) {
@@ -907,7 +901,7 @@ __global__ __launch_bounds__(256, 2) void wgrad2_kernel(WgArgs a) {
 }
 
 // Split-bf16 weight gradient (fp32-accurate on the bf16 matrix cores; the x = hi + mid + lo split and
-// the 6-product sum of conv3x3_igemm.hip's x3 kernel). dW[co][ci][tap] = sum_pix dY[co][pix] *
+// the 6-product sum of conv_x3.hip's x3 kernel). dW[co][ci][tap] = sum_pix dY[co][pix] *
 // X[ci][pix + tap] as a GEMM with K = pixels, v_mfma_f32_32x32x16_bf16:
 //  * A = dY (rows co): LDS [plane][co][pixel] (row pitch 144 B: conflict-free ds_read_b128 of 8
 //    consecutive pixels per lane);
@@ -923,16 +917,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// as split3 in conv3x3_igemm.hip (finite overflow of hi clamped; non-finite x carried by hi alone)
-__device__ __forceinline__ void wg_split3(float x, bf16_t& hi, bf16_t& mid, bf16_t& lo) {
-  const bool finite = fabsf(x) <= 3.402823466e38f;
-  hi = (bf16_t)x;
-  if (finite && !(fabsf((float)hi) <= 3.402823466e38f)) hi = (bf16_t)copysignf(3.38953139e38f, x);
-  float r = finite ? x - (float)hi : 0.f;
-  mid = (bf16_t)r;
-  lo = (bf16_t)(r - (float)mid);
-}
 
 template <int UP>
 struct Wg3Cfg {
@@ -1012,7 +996,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(WgArgs a) {
       if (e < C::XI) {                                                                                    \
         const int p = e % NPIX, g = (HALF) * 4 + e / NPIX;                                                \
         bf16x8_t pv[3];                                                                                   \
-        ast_x3::split8(xv[k], pv[0], pv[1], pv[2]);  /* = wg_split3 per value, paired conversions */    \
+        ast_x3::split8(xv[k], pv[0], pv[1], pv[2]);  /* = split3 per value, paired conversions */       \
         const int off = (g >> 2) * C::XHALF + p * C::XROW + (g & 3) * 16;                                 \
         _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                  \
           *reinterpret_cast<u32x4_t*>(wg3_smem + pl * C::XPLANE + off) = __builtin_bit_cast(u32x4_t, pv[pl]); \
@@ -1116,9 +1100,6 @@ const int g_rowpar = [] {
 }();
 
 int grid1(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int round_up(int a, int b) { return cdiv(a, b) * b; }
-
 }  // namespace
 
 extern "C" {

@@ -25,11 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "conv_common.h"
 #include "x3.h"
 #include "cin3.h"
 
 namespace {
 
+using ast_conv::relu_f;  // relu(NaN) = NaN
 using ast_x3::bf16;
 using ast_x3::bf16x8;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -49,6 +51,7 @@ struct C3 {
 };
 
 // source index of padded coordinate v (may be -1 or n): zero padding -1 outside, ReflectionPad2d(1)
+// (conv_common.h's src_index<1> without the upsample parameter: this kernel never upsamples)
 __device__ __forceinline__ int src_index1(int v, int n, int reflect) {
   if (v >= 0 && v < n) return v;
   if (!reflect) return -1;
@@ -56,11 +59,9 @@ __device__ __forceinline__ int src_index1(int v, int n, int reflect) {
   return r < 0 ? 0 : (r >= n ? n - 1 : r);
 }
 
-__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }  // relu(NaN) = NaN
-
 __device__ __forceinline__ unsigned short bits(bf16 v) { return __builtin_bit_cast(unsigned short, v); }
 
-// DG: the input-gradient epilogue of conv3x3_igemm.hip dgrad_epi_one (same arithmetic; y_pre only, no
+// DG: the input-gradient epilogue of conv_common.h dgrad_epi_one (same arithmetic; y_pre only, no
 // bias), its mask loaded before the block's MFMAs; otherwise bias + y_pre / y_act. The epilogue
 // modes are template / wave-uniform branches around whole store loops: a per-element choice between
 // the store-only and the load-using paths made the compiler wait on vmcnt -- which on gfx9 also

@@ -1,6 +1,6 @@
 // Side-by-side image packing for small-plane 3x3 convolutions (ops.conv3x3, zero padding).
-// The implicit-GEMM conv kernel (conv3x3_igemm.hip) tiles each output row in 32-pixel MFMA M
-// tiles, so a 20- or 10-pixel-wide plane leaves 38-69% of every tile idle (the AutoEncoder loss
+// The implicit-GEMM conv kernels (conv3x3_igemm.hip, conv_x3.hip) tile each output row in 32-pixel
+// MFMA M tiles, so a 20- or 10-pixel-wide plane leaves 38-69% of every tile idle (the AutoEncoder loss
 // network's 512-channel layers at 160x160 input). G images placed side by side with `gap` zero
 // columns between them form one wider plane whose zero-padded 3x3 conv equals the G separate
 // zero-padded convs (a tap that leaves an image reads a gap zero, exactly like the padding);

@@ -1,6 +1,6 @@
 // Split-bf16 ("x3") helpers shared by the fp32-accurate MFMA kernels: an fp32 value is carried as
 // three bf16 terms x = hi + mid + lo (exact for finite x), and a product as the six largest term
-// products, folded into three v_mfma_f32_16x16x32_bf16 per 16 channels of K (see conv3x3_igemm.hip
+// products, folded into three v_mfma_f32_16x16x32_bf16 per 16 channels of K (see conv_x3.hip
 // M16 and mbtrain.hip gemm_x3_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +13,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // finite |x| above bf16's largest value would round hi to inf: hi is clamped to that value and the
 // remainder stays exact. Non-finite x: hi = x, mid = lo = 0 (inf and NaN propagate through hi).
+// The MFMA also multiplies hi by the weight's mid and lo terms, which are often exactly 0, so an
+// output reached by an inf input is +-inf (as torch's inf * w) or NaN; NaN inputs give NaN, as in
+// torch. tests/test_gpu_parity.py pins both behaviours. The only definition: the conv kernels, the
+// weight packs and the weight gradient all split through this one.
 __device__ __forceinline__ void split3(float x, bf16& hi, bf16& mid, bf16& lo) {
   const bool finite = fabsf(x) <= 3.402823466e38f;
   hi = (bf16)x;

@@ -119,7 +119,7 @@ def up2c_enabled() -> bool:
 def pack_conv3x3(weight: torch.Tensor, up2c: bool = False) -> torch.Tensor:
     """Repack a [cout, cin, 3, 3] filter bank into the kernel's [cin_pad][9][cout_pad] layout.
     up2c: the extended pack -- the usual one with the collapsed slab of the upsampled reflect-pad
-    conv (2x2 taps per output phase, csrc/conv3x3_igemm.hip) appended; conv3x3 accepts either."""
+    conv (2x2 taps per output phase, csrc/conv_up2c.hip) appended; conv3x3 accepts either."""
     w = _dev(weight, "weight")
     if w.dim() != 4 or w.shape[2:] != (3, 3):
         raise HipOpError(f"conv3x3 weight must be [cout, cin, 3, 3], got {tuple(w.shape)}")

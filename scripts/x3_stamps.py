@@ -2,7 +2,7 @@
 """Phase timing of the split-bf16 conv (conv3x3_x3_kernel<M16>) from in-kernel clock stamps.
 
 Diagnostic only: needs the X3_STAMP build (bash scripts/build_variants.sh stamp "-DX3_STAMP=1"
-conv3x3_igemm.hip), which this script selects through AST_HIP_LIB. The stamps never reach an output.
+conv_x3.hip), which this script selects through AST_HIP_LIB. The stamps never reach an output.
 python scripts/x3_stamps.py OUTDIR [cfg n cin h w cout up pad pool]
 Writes OUTDIR/x3_stamps_<shape>.npz (raw records) and prints the per-phase summary
 (scripts/x3_stamps_summary.py does the same from the npz)."""

@@ -3,7 +3,7 @@
 clock stamps, at the phase boundaries scripts/x3_stamps.py reads for the 9-tap kernel.
 
 Diagnostic only: needs the X3_STAMP build (bash scripts/build_variants.sh stamp "-DX3_STAMP=1"
-conv3x3_igemm.hip), selected through AST_HIP_LIB. The stamps never reach an output.
+conv_up2c.hip), selected through AST_HIP_LIB. The stamps never reach an output.
 python scripts/x3_stamps_up2c.py OUTDIR TILE [n cin h_in w_in cout]     (TILE = 8 | 4)
 Writes OUTDIR/up2c_stamps_t<TILE>_<shape>.npz (raw records) and prints the per-phase summary
 (python scripts/x3_stamps_up2c.py FILE.npz prints it again from the records)."""

@@ -206,7 +206,7 @@ def test_conv3x3_nan_propagates(hip_device):
 
 
 def test_conv3x3_split_bf16_nonfinite_and_overflow(hip_device):
-    """The split-bf16 kernel's contract for extreme inputs (csrc/conv3x3_igemm.hip split3):
+    """The split-bf16 kernel's contract for extreme inputs (csrc/x3.h split3):
     * a finite input above bf16's largest value (3.3895e38) is split exactly (hi clamped), so a
       single large pixel gives the same output as torch, to fp32 accuracy;
     * an inf input gives a non-finite value at every output it reaches: +-inf with torch's sign,
