@@ -68,8 +68,11 @@ class FusedAdam(torch.optim.Optimizer):
                  max_grad_norm=None, error_if_nonfinite=False):
         if weight_decay != 0.0:
             raise ValueError("FusedAdam: weight_decay is not supported (the reference uses 0)")
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0.0, amsgrad=False, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None)
+        # the installed torch.optim.Adam's own defaults (newer releases add keys, such as
+        # decoupled_weight_decay), so a state dict's param_groups carry exactly the keys torch's do
+        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).defaults)
+        defaults.update(weight_decay=0.0, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                        differentiable=False, fused=None)
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
         self.error_if_nonfinite = error_if_nonfinite
@@ -97,6 +100,15 @@ class FusedAdam(torch.optim.Optimizer):
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        # torch keeps one step count per parameter: those of a group that missed steps (no gradient
+        # then) take their own bias corrections, in a launch of their own (usually there is one set)
+        split = []
+        for gi, group, params in groups:
+            by_step = {}
+            for p in params:
+                by_step.setdefault(float(self.state[p]["step"]), []).append(p)
+            split += [((gi, k), group, ps) for k, ps in enumerate(by_step.values())]
+        groups = split
         tables = []
         for gi, group, params in groups:
             table = self._tables.setdefault(gi, _Table())
@@ -147,6 +159,9 @@ class FusedAdam(torch.optim.Optimizer):
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if len({float(self.state[p]["step"]) for p in params}) != 1:
+                raise RuntimeError("FusedAdam.prepare_static: the parameters of a group differ in their step counts; "
+                                   "the capturable step keeps one device step count per group")
             table = _Table()
             nbytes = int(lib().ast_optim_table_bytes(len(params)))
             table.host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
