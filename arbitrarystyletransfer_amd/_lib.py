@@ -78,6 +78,13 @@ SIGNATURES = {
     "ast_patch_gather_guided_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ast_style_swap_guided_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "ast_style_swap_guided_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
+    "ast_kmeans_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_kmeans_seed_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_kmeans_assign_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ast_kmeans_update_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_kmeans_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "ast_label_mode_filter_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "ast_label_mode_filter_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "ast_conv3x3_pack_weights_ex_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ast_conv_act_backward_f32": (_i, [_p, _p, _p, _p, _p, _ll, _i, _i, _p]),
     "ast_relu_mask_f32": (_i, [_p, _p, _p, _ll, _p]),

@@ -39,6 +39,9 @@ wct                     -- (whitening and colouring transform)       raises NotI
 wct_regions             -- (WCT per region, mix of a style bank)     raises NotImplementedError
 style_swap              -- (patch-matching style swap)               raises NotImplementedError
 style_swap_guided       -- (class-guided style swap over a bank)     raises NotImplementedError
+kmeans                  -- (feature k-means: centroids, labels, counts)   raises NotImplementedError
+kmeans_assign           -- (nearest centroid per pixel, uint8 labels)     raises NotImplementedError
+label_mode_filter       -- (3x3 majority vote over uint8 label maps)      --
 The MobileNet inference ops fold eval-mode BatchNorm; training runs the composable kernels of
 mbtrain.py (their own autograd), as the drop-in DepthWiseConv does.
 """
@@ -808,8 +811,60 @@ def _style_swap_guided_backward(ctx, g):
 register_autograd("ast_hip::style_swap_guided", _style_swap_guided_backward)
 
 
+# ------------------------------------------------------------------------------------------------
+# Feature k-means and the label mode filter (csrc/kmeans.hip; inference only)
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::kmeans", mutates_args=())
+def kmeans(x: Tensor, k: int, iters: int, init: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """Lloyd's k-means over the points of a bank [B, C, H, W]: centroids [k, C], labels uint8 [B, H, W], counts [k]."""
+    return ops.kmeans(x, k, iters=iters, init=init)
+
+
+@register_fake("ast_hip::kmeans")
+def _(x, k, iters, init):
+    b, c, h, w = x.shape
+    return (x.new_empty((k, c)), x.new_empty((b, h, w), dtype=torch.uint8), x.new_empty((k,), dtype=torch.int32))
+
+
+def _kmeans_backward(ctx, *g):
+    raise NotImplementedError("ast_hip::kmeans has no backward: the clustering is inference-only")
+
+
+register_autograd("ast_hip::kmeans", _kmeans_backward)
+
+
+@custom_op("ast_hip::kmeans_assign", mutates_args=())
+def kmeans_assign(x: Tensor, centroids: Tensor) -> Tensor:
+    """The nearest of the centroids [K, C] for every pixel of x [B, C, H, W]: uint8 [B, H, W]."""
+    return ops.kmeans_assign(x, centroids)
+
+
+@register_fake("ast_hip::kmeans_assign")
+def _(x, centroids):
+    return x.new_empty((x.shape[0], x.shape[2], x.shape[3]), dtype=torch.uint8)
+
+
+def _kmeans_assign_backward(ctx, g):
+    raise NotImplementedError("ast_hip::kmeans_assign has no backward: labels are not differentiable")
+
+
+register_autograd("ast_hip::kmeans_assign", _kmeans_assign_backward)
+
+
+@custom_op("ast_hip::label_mode_filter", mutates_args=())
+def label_mode_filter(labels: Tensor, regions: int, passes: int) -> Tensor:
+    """`passes` rounds of a 3x3 majority vote over uint8 label maps [N, H, W]."""
+    return ops.label_mode_filter(labels, regions, passes=passes)
+
+
+@register_fake("ast_hip::label_mode_filter")
+def _(labels, regions, passes):
+    return torch.empty_like(labels)
+
+
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
                   "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "wct_regions", "style_swap",
-                  "style_swap_guided"]
+                  "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]

@@ -433,6 +433,82 @@ class VGGDecoder(nn.Sequential):
         return x
 
 
+class AutoRegions:
+    """Ask a regional method to make its own region maps: `labels=AutoRegions(4)` in place of a uint8
+    label map. The style bank's relu4_1 features are clustered into `regions` sub-styles by k-means
+    (ops.kmeans: maximin seeds, `iters` Lloyd rounds), every content pixel is assigned to the nearest
+    of them (ops.kmeans_assign), and both label maps are smoothed by `smooth` passes of the 3x3 mode
+    filter (ops.label_mode_filter) -- the clustering stage of Multimodal Style Transfer (Zhang et
+    al., ICCV 2019). normalize=True clusters the per-image ops.mean_variance_norm of the maps, which
+    makes content and style features comparable; False the maps themselves. regions in
+    1..ops.MAX_REGIONS, iters >= 0, smooth >= 0 (ValueError otherwise); the object is immutable."""
+
+    __slots__ = ("regions", "iters", "smooth", "normalize")
+
+    def __init__(self, regions: int = 3, iters: int = ops.KMEANS_DEFAULT_ITERS, smooth: int = 1,
+                 normalize: bool = True):
+        def integer(v):
+            return isinstance(v, int) and not isinstance(v, bool)
+        if not integer(regions) or not 1 <= regions <= ops.MAX_REGIONS:
+            raise ValueError(f"regions must be an int in 1..{ops.MAX_REGIONS}, got {regions!r}")
+        if not integer(iters) or iters < 0:
+            raise ValueError(f"iters must be an int >= 0, got {iters!r}")
+        if not integer(smooth) or smooth < 0:
+            raise ValueError(f"smooth must be an int >= 0, got {smooth!r}")
+        if not isinstance(normalize, bool):
+            raise ValueError(f"normalize must be a bool, got {normalize!r}")
+        for name, v in (("regions", regions), ("iters", iters), ("smooth", smooth), ("normalize", normalize)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("AutoRegions is immutable")
+
+    def __repr__(self):
+        return (f"AutoRegions(regions={self.regions}, iters={self.iters}, smooth={self.smooth}, "
+                f"normalize={self.normalize})")
+
+
+def auto_region_weights(counts):
+    """The region weights of AutoRegions from the pixel counts [K, S] of region k in style s (after
+    smoothing): (weights float64 CPU [K, S], dead bool [K]). w[k, s] = the count where it is at least
+    2, else 0 -- a standard deviation or a covariance needs two pixels. A region whose row is all zero
+    is dead: the caller relabels it 255 in both maps, so nothing reads its row, which is set to 1 / S
+    to stay a valid mix. Rows are not normalised here (region_weights does that)."""
+    c = torch.as_tensor(counts).to(torch.float64).cpu()
+    if c.dim() != 2 or c.numel() == 0:
+        raise ValueError(f"counts must be a non-empty [K, S] array, got {tuple(c.shape)}")
+    w = torch.where(c >= 2, c, torch.zeros_like(c))
+    dead = w.sum(dim=1) <= 0
+    w[dead] = 1.0 / c.shape[1]
+    return w, dead
+
+
+def _auto_regions(f_c, f_s, auto: AutoRegions):
+    """(labels uint8 [N, h, w], style_labels uint8 [S, hs, ws], weights float64 CPU [K, S]) of
+    AutoRegions from the relu4_1 maps of the content batch and of the style bank."""
+    k = auto.regions
+    key_c, key_s = (ops.mean_variance_norm(f_c), ops.mean_variance_norm(f_s)) if auto.normalize else (f_c, f_s)
+    cen, sl, _ = ops.kmeans(key_s, k, iters=auto.iters)
+    cl = ops.kmeans_assign(key_c, cen)
+    if auto.smooth:
+        cl = ops.label_mode_filter(cl, k, passes=auto.smooth)
+        sl = ops.label_mode_filter(sl, k, passes=auto.smooth)
+    every = torch.arange(256, device=sl.device, dtype=torch.uint8)
+    ids, none = every[:k], every[255:]
+
+    def counts(maps):                                                 # [maps, K], after smoothing
+        return (maps.flatten(1).unsqueeze(1) == ids.view(1, k, 1)).sum(dim=2)
+
+    def relabel(maps, keep):                                          # keep [maps or 1, K]: the others become 255
+        lut = torch.cat([torch.where(keep, ids, none), every[k:].expand(keep.shape[0], -1)], dim=1)
+        return lut.expand(maps.shape[0], -1).gather(1, maps.flatten(1).long()).view_as(maps)
+
+    w, dead = auto_region_weights(counts(sl).t().cpu())               # the one host synchronisation
+    live = ~dead.to(sl.device).unsqueeze(0)
+    # a content sample's region of one pixel has no standard deviation either: it passes through too
+    return relabel(cl, live & (counts(cl) >= 2)), relabel(sl, live), w
+
+
 class AdaINStyleTransfer(nn.Module):
     """encoder (VGG19 to relu4_1) -> AdaIN -> alpha blend -> mirrored decoder.
 
@@ -449,6 +525,8 @@ class AdaINStyleTransfer(nn.Module):
     encoder and decoder, whatever the transform; `stylize_swap_regions` is its guided form over a
     bank of styles, steered by the label maps of `stylize_regions`. `stylize_regions_wct` is
     `stylize_regions` with WCT per region (ops.wct_regions), also whatever the transform.
+    The three regional methods take `labels=AutoRegions(k)` in place of label maps: the maps, the
+    style maps and the weights then come from a k-means over the style features (`auto_labels`).
     """
 
     TRANSFORMS = ("adain", "efdm", "wct")
@@ -510,6 +588,38 @@ class AdaINStyleTransfer(nn.Module):
             return _luma_transfer(out, content_img)
         return out
 
+    def _inference_only(self, what, *imgs):
+        if torch.is_grad_enabled() and (any(i.requires_grad for i in imgs)
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(f"{what} is inference-only; run it under torch.no_grad()")
+
+    def auto_labels(self, content_img, style_imgs, auto: AutoRegions = AutoRegions()):
+        """The region maps that `labels=auto` gives the regional methods, for content_img [N, 3, H, W]
+        and the style bank style_imgs [S, 3, Hs, Ws]: (labels uint8 [N, h, w], style_labels uint8
+        [S, hs, ws], weights float64 CPU [K, S]) at relu4_1 resolution, in the form stylize_regions,
+        stylize_regions_wct and stylize_swap_regions take. The bank's features are clustered together
+        (see AutoRegions), so region k is the same sub-style in every map. weights[k, s] is the number
+        of pixels of region k in style s after smoothing, 0 below two pixels; a region with no style
+        pixels left is relabelled 255 in both maps (its content passes through, its style pixels
+        leave the bank) and its row is 1 / S. A region with a single pixel in one content sample is
+        relabelled 255 in that sample for the same reason: one pixel has no standard deviation.
+        Fetching the style counts is the one host synchronisation. Inference only."""
+        self._inference_only("auto_labels", content_img, style_imgs)
+        if not isinstance(auto, AutoRegions):
+            raise ValueError(f"auto must be an AutoRegions, got {type(auto).__name__}")
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError("auto_labels needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        return _auto_regions(self.encoder(content_img)[0], self.encoder(style_imgs)[0], auto)
+
+    @staticmethod
+    def _auto_request(labels, style_labels, weights=None):
+        """labels when it is an AutoRegions (style_labels and weights must then be None), else None."""
+        if not isinstance(labels, AutoRegions):
+            return None
+        if style_labels is not None or weights is not None:
+            raise ValueError("labels=AutoRegions(...) makes style_labels and weights itself: leave both None")
+        return labels
+
     def stylize_swap_regions(self, content_img, style_imgs, labels=None, style_labels=None, alpha: float = 1.0,
                              normalize: bool = False, preserve_color: bool = False):
         """Guided style swap (ops.style_swap_guided on the relu4_1 maps): content_img [N, 3, H, W]
@@ -523,17 +633,21 @@ class AdaINStyleTransfer(nn.Module):
         Both: a patch labelled k takes its best patch among those labelled k in any style ("sky
         takes sky"); label 255 (any label >= ops.SWAP_MAX_CLASSES) in a style map removes the patch
         from the bank, in the content map it passes the content through.
-        style_labels without labels: ValueError. normalize as stylize_swap, preserve_color as forward."""
+        style_labels without labels: ValueError. normalize as stylize_swap, preserve_color as forward.
+        labels=AutoRegions(...): both maps as auto_labels makes them (style_labels must be None)."""
         if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
                                         or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_swap_regions is inference-only; run it under torch.no_grad()")
         if content_img.dim() != 4 or style_imgs.dim() != 4:
             raise ValueError("stylize_swap_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        auto = self._auto_request(labels, style_labels)
         if style_labels is not None and labels is None:
             raise ValueError("style_labels without labels: give the content's label map too")
         n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
         f_c = self.encoder(content_img)[0]
         f_s = self.encoder(style_imgs)[0]
+        if auto is not None:
+            labels, style_labels, _ = _auto_regions(f_c, f_s, auto)
         dev = f_c.device
         if labels is None:
             cc = torch.zeros((n, f_c.shape[2] - 2, f_c.shape[3] - 2), device=dev, dtype=torch.uint8)
@@ -596,20 +710,29 @@ class AdaINStyleTransfer(nn.Module):
         None: region k takes style k (K = S), or equal weights when labels is None.
         style_labels: uint8 [S, Hs, Ws] with the same region ids: region k then takes the
         statistics of each style's own region k instead of the whole style map (K * S <= 64).
-        preserve_color as in forward."""
+        preserve_color as in forward.
+        labels=AutoRegions(...): labels, style_labels and weights as auto_labels makes them from the
+        features encoded here (style_labels and weights must be None; K * S <= 64)."""
         self._needs_statistics("stylize_regions")
         if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
                                         or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_regions is inference-only; run it under torch.no_grad()")
         if content_img.dim() != 4 or style_imgs.dim() != 4:
             raise ValueError("stylize_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        auto = self._auto_request(labels, style_labels, weights)
         n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
-        w = region_weights(weights, n, s, single_region=labels is None)
-        k = int(w.shape[1])
-        if s * (k if style_labels is not None else 1) > ops.MAX_STYLE_ROWS:
+        if auto is None:
+            w = region_weights(weights, n, s, single_region=labels is None)
+            k = int(w.shape[1])
+        else:
+            k = auto.regions
+        if s * (k if style_labels is not None or auto is not None else 1) > ops.MAX_STYLE_ROWS:
             raise ValueError(f"at most {ops.MAX_STYLE_ROWS} rows of style statistics (S, or K * S with style_labels)")
         f_c = self.encoder(content_img)[0]
         f_s = self.encoder(style_imgs)[0]
+        if auto is not None:
+            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
+            w = region_weights(weights, n, s)
         if labels is None:
             lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
         else:
@@ -646,18 +769,24 @@ class AdaINStyleTransfer(nn.Module):
         stylize_regions (labels=None: one region, plain style interpolation; weights=None: region k
         takes style k, or equal weights when labels is None). With style_labels region k takes the
         statistics of each style's own region k; where a style of non-zero weight has fewer than 2
-        such pixels, the region keeps the content's features. eps_rel and iters as WCT."""
+        such pixels, the region keeps the content's features. eps_rel and iters as WCT.
+        labels=AutoRegions(...) as in stylize_regions."""
         if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
                                         or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stylize_regions_wct is inference-only; run it under torch.no_grad()")
         if content_img.dim() != 4 or style_imgs.dim() != 4:
             raise ValueError("stylize_regions_wct needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        auto = self._auto_request(labels, style_labels, weights)
         n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
         if s > ops.MAX_STYLE_ROWS:
             raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
-        w = region_weights(weights, n, s, single_region=labels is None)
+        if auto is None:
+            w = region_weights(weights, n, s, single_region=labels is None)
         f_c = self.encoder(content_img)[0]
         f_s = self.encoder(style_imgs)[0]
+        if auto is not None:
+            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
+            w = region_weights(weights, n, s)
         if labels is None:
             lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
         else:

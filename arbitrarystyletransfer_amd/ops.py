@@ -840,6 +840,130 @@ def style_swap_guided(content: torch.Tensor, styles: torch.Tensor, content_class
     return (out, index) if return_index else out
 
 
+# Feature k-means and the label mode filter (csrc/kmeans.hip): the limits of ast_hip.h
+KMEANS_MAX_C = 1024
+KMEANS_MAX_POINTS = 1 << 24
+KMEANS_DEFAULT_ITERS = 10
+
+
+def _kmeans_bank(x: torch.Tensor, what: str):
+    """An fp32 device bank [B, C, H, W] within the limits: (x, b, c, h, w)."""
+    x = _dev(x, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise HipOpError(f"{what} needs a non-empty NCHW bank, got {tuple(x.shape)}")
+    b, c, h, w = (int(s) for s in x.shape)
+    if c > KMEANS_MAX_C or b * h * w > KMEANS_MAX_POINTS:
+        raise HipOpError(f"{what}: at most {KMEANS_MAX_C} channels and {KMEANS_MAX_POINTS} points, got "
+                         f"{c} channels and {b * h * w} points")
+    return x, b, c, h, w
+
+
+def _kmeans_centroids(cen, c: int, device, name: str):
+    """fp32 centroids [K, C] on `device`, K in 1..MAX_REGIONS: (centroids, k)."""
+    cen = _dev(cen, name)
+    if cen.dim() != 2 or cen.shape[1] != c or not 1 <= cen.shape[0] <= MAX_REGIONS or cen.device != device:
+        raise HipOpError(f"{name} must be [K <= {MAX_REGIONS}, C={c}] on {device}, got {tuple(cen.shape)} "
+                         f"on {cen.device}")
+    return cen, int(cen.shape[0])
+
+
+def _count(v, name: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        raise HipOpError(f"{name} must be an int >= 0, got {v!r}")
+    return v
+
+
+def kmeans_seed(x: torch.Tensor, k: int):
+    """The k maximin seeds of the bank x [B, C, H, W] (point g = b * H * W + pixel, all points together):
+    the point farthest from the mean of all points, then repeatedly the point farthest from the seeds
+    so far; ties to the lowest g. int32 [k] of global point indices."""
+    k = _regions(k)
+    x, b, c, h, w = _kmeans_bank(x, "kmeans_seed")
+    L = lib()
+    nbytes = int(L.ast_kmeans_workspace_bytes(b, c, h, w, k))
+    wsb = _ws_bytes(nbytes, "kmeans workspace", x.device)
+    seeds = torch.empty((k,), device=x.device, dtype=torch.int32)
+    check(L.ast_kmeans_seed_f32(ptr(x), ptr(seeds), b, c, h, w, k, ptr(wsb), nbytes, stream_ptr(x.device)),
+          "kmeans_seed")
+    return seeds
+
+
+def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
+    """The nearest of centroids [K, C] for every point of x [B, C, H, W], by the squared distance over the
+    channels: uint8 [B, H, W]. The lowest k wins on equal distances; a NaN never wins, and a point without
+    a winner gets 255, the "no region" label of the regional ops. One launch."""
+    x, b, c, h, w = _kmeans_bank(x, "kmeans_assign")
+    cen, k = _kmeans_centroids(centroids, c, x.device, "centroids")
+    labels = torch.empty((b, h, w), device=x.device, dtype=torch.uint8)
+    check(_timed(f"kmeans_assign {c}ch {b}x{h}x{w} K{k}", -(4 * x.numel() + labels.numel()), x.device,
+                 lambda: lib().ast_kmeans_assign_f32(ptr(x), ptr(cen), ptr(labels), b, c, h, w, k,
+                                                     stream_ptr(x.device))), "kmeans_assign")
+    return labels
+
+
+def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor):
+    """One centroid update: (centroids [K, C], counts int32 [K]), centroid k the mean of the points of x
+    labelled k (labels uint8 [B, H, W]; a label >= K belongs to no cluster), a cluster without points
+    keeping its row of `centroids` bit for bit. Deterministic: partial sums per workgroup, added in a
+    fixed order, no atomics."""
+    x, labels, b, c, h, w = _map_and_labels(x, labels, "x")
+    x, b, c, h, w = _kmeans_bank(x, "kmeans_update")
+    cen, k = _kmeans_centroids(centroids, c, x.device, "centroids")
+    L = lib()
+    nbytes = int(L.ast_kmeans_workspace_bytes(b, c, h, w, k))
+    wsb = _ws_bytes(nbytes, "kmeans workspace", x.device)
+    out = torch.empty_like(cen)
+    counts = torch.empty((k,), device=x.device, dtype=torch.int32)
+    check(L.ast_kmeans_update_f32(ptr(x), ptr(labels), ptr(cen), ptr(out), ptr(counts), b, c, h, w, k, ptr(wsb),
+                                  nbytes, stream_ptr(x.device)), "kmeans_update")
+    return out, counts
+
+
+def kmeans(x: torch.Tensor, k: int, iters: int = KMEANS_DEFAULT_ITERS, init: torch.Tensor = None):
+    """Deterministic k-means (Lloyd) over the points of the bank x [B, C, H, W]: (centroids [k, C],
+    labels uint8 [B, H, W], counts int32 [k]). The initial centroids are the points at the maximin
+    seeds (kmeans_seed), or `init` [k, C]; then `iters` rounds of assign and update -- per round one
+    launch that reads the bank once, and a small reduction -- and one final assign, so labels and counts
+    belong to the returned centroids. The number of rounds is fixed, there is no convergence test and
+    no host synchronisation (the op can be captured into a graph); iters=0 gives the initial centroids
+    and one assign. The default of 10 rounds is a definitional constant, not a measured optimum."""
+    k, iters = _regions(k), _count(iters, "iters")
+    x, b, c, h, w = _kmeans_bank(x, "kmeans")
+    if init is not None:
+        init, ki = _kmeans_centroids(init, c, x.device, "init")
+        if ki != k:
+            raise HipOpError(f"init must have k = {k} rows, got {ki}")
+    L = lib()
+    nbytes = int(L.ast_kmeans_workspace_bytes(b, c, h, w, k))
+    wsb = _ws_bytes(nbytes, "kmeans workspace", x.device)
+    cen = torch.empty((k, c), device=x.device, dtype=torch.float32)
+    labels = torch.empty((b, h, w), device=x.device, dtype=torch.uint8)
+    counts = torch.empty((k,), device=x.device, dtype=torch.int32)
+    # algorithmic bytes: the bank once per round and once more for the final assign (the seeding's k + 1
+    # reads on top when there is no init), the labels written each time
+    reads = iters + 1 + (0 if init is not None else k + 1)
+    check(_timed(f"kmeans {c}ch {b}x{h}x{w} K{k} x{iters}", -(reads * 4 * x.numel() + (iters + 1) * labels.numel()),
+                 x.device, lambda: L.ast_kmeans_f32(ptr(x), ptr(init), ptr(cen), ptr(labels), ptr(counts), None, b, c,
+                                                    h, w, k, iters, ptr(wsb), nbytes, stream_ptr(x.device))), "kmeans")
+    return cen, labels, counts
+
+
+def label_mode_filter(labels: torch.Tensor, regions: int, passes: int = 1):
+    """`passes` rounds of a 3x3 majority vote over uint8 label maps [N, H, W] (window clipped at the
+    borders): only labels < regions vote, the most frequent wins, on a tie the centre's own label if it
+    is among the tied, else the lowest; a pixel labelled >= regions passes through. Exact."""
+    regions, passes = _regions(regions), _count(passes, "passes")
+    labels = _labels(labels, "labels")
+    n, h, w = (int(s) for s in labels.shape)
+    L = lib()
+    nbytes = int(L.ast_label_mode_filter_workspace_bytes(n, h, w, passes))
+    wsb = _ws_bytes(nbytes, "label_mode_filter workspace", labels.device)
+    out = torch.empty_like(labels)
+    check(L.ast_label_mode_filter_u8(ptr(labels), ptr(out), n, h, w, regions, passes, ptr(wsb), nbytes,
+                                     stream_ptr(labels.device)), "label_mode_filter")
+    return out
+
+
 def adain_bf16(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, swap_style_stats: bool = True):
     """AdaIN on bf16 maps (fp32 statistics and arithmetic, bf16 result)."""
     content = _dev_typed(content, "content_map", torch.bfloat16)

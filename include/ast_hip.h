@@ -443,6 +443,60 @@ int ast_style_swap_guided_f32(const float* content_key, const float* style_keys,
                               float* score_or_null, int n, int s, int c, int hc, int wc, int hs, int ws,
                               double alpha, void* workspace, long long workspace_bytes, void* stream);
 
+/* Feature k-means and the label mode filter (csrc/kmeans.hip; an extension, no reference counterpart):
+ * the stage that makes the uint8 label maps of the regional transforms above from the features
+ * themselves, as Multimodal Style Transfer (Zhang et al., ICCV 2019) clusters the style's relu4_1
+ * features into sub-styles and assigns every content pixel to one of them.
+ * A bank is x [b, c, h, w], fp32 dense NCHW: point g = map * h w + pixel is the c-vector at that pixel
+ * and all b h w points are clustered together. 1 <= c <= AST_KMEANS_MAX_C, h, w >= 1,
+ * b h w <= AST_KMEANS_MAX_POINTS. Centroids are [k, c] fp32, 1 <= k <= AST_KMEANS_MAX_K (= AST_MAX_REGIONS).
+ * d(g, j) = sum over channels of (x - centroid_j)^2 in fp32, a fixed summation order that depends on
+ * the shape alone, so equal centroids give equal distances in bits.
+ * Assign: label(g) = the j of least d, the lowest j on equal distances; a distance replaces the running
+ * (+inf, 255) only when strictly smaller, so a NaN never wins and a point without a winner gets label
+ * 255 and belongs to no cluster (the "label >= K" convention above). labels is uint8 [b, h, w].
+ * Update: from x, labels and the previous centroids, sum_j = the fp32 sum of the points labelled j and
+ * count_j (int32) their number; centroid_j = sum_j / count_j, and a cluster of count 0 keeps its previous
+ * centroid in bits. centroids may be prev_centroids. Workgroups write partial sums into the workspace
+ * and a second launch adds them in a fixed order: no floating-point atomics.
+ * Seed ("maximin"): m = the mean of all points; seed 0 = the g of largest d(g, m); seed j = the g of
+ * largest min over the earlier seeds of d(g, seed); ties to the lowest g; a point whose distance is a
+ * NaN is never chosen, and 0 is returned where none compares. seeds is int32 [k], global point indices.
+ * Lloyd, ast_kmeans_f32: the initial centroids are bitwise copies of init [k, c], or, with init null,
+ * of the points at the maximin seeds (also written to seeds_or_null when given); then `iters` rounds of
+ * assign and update -- one launch that stages a tile of pixels, labels it and adds it into the
+ * workgroup's partial sums, so the bank is read once per round, and the small reduction --, then one
+ * final assign, so the returned labels and counts belong to the returned centroids. It equals the
+ * composition of the three stages bit for bit. The number of launches is fixed: no convergence test,
+ * no host synchronisation, no allocation; the op can be captured into a graph.
+ * One workspace query serves every entry. AST_E_NULLPTR: a null pointer (but the optional ones).
+ * AST_E_SHAPE: a size <= 0, too many points, a short workspace. AST_E_UNSUPPORTED: c or k over the limit,
+ * iters < 0. The query returns the same negative codes. All checks run before the first launch. */
+#define AST_KMEANS_MAX_K 8
+#define AST_KMEANS_MAX_C 1024
+#define AST_KMEANS_MAX_POINTS (1 << 24)
+long long ast_kmeans_workspace_bytes(int b, int c, int h, int w, int k);
+int ast_kmeans_seed_f32(const float* x, int* seeds, int b, int c, int h, int w, int k, void* workspace,
+                        long long workspace_bytes, void* stream);
+int ast_kmeans_assign_f32(const float* x, const float* centroids, unsigned char* labels, int b, int c,
+                          int h, int w, int k, void* stream);
+int ast_kmeans_update_f32(const float* x, const unsigned char* labels, const float* prev_centroids,
+                          float* centroids, int* counts, int b, int c, int h, int w, int k,
+                          void* workspace, long long workspace_bytes, void* stream);
+int ast_kmeans_f32(const float* x, const float* init_or_null, float* centroids, unsigned char* labels,
+                   int* counts, int* seeds_or_null, int b, int c, int h, int w, int k, int iters,
+                   void* workspace, long long workspace_bytes, void* stream);
+
+/* `passes` rounds of a 3x3 majority vote over uint8 label maps [n, h, w] (out must not be labels): the
+ * window is clipped at the borders, only labels < regions vote, the most frequent label wins; on a tie
+ * the centre's own label if it is among the tied, else the lowest. A pixel whose own label is
+ * >= regions passes through. passes = 0 copies. More than one pass needs the workspace of the query.
+ * regions outside 1..AST_MAX_REGIONS or passes < 0: AST_E_UNSUPPORTED. */
+long long ast_label_mode_filter_workspace_bytes(int n, int h, int w, int passes);
+int ast_label_mode_filter_u8(const unsigned char* labels, unsigned char* out, int n, int h, int w,
+                             int regions, int passes, void* workspace, long long workspace_bytes,
+                             void* stream);
+
 /* out = (x - mean[p]) / std[p] per plane (mean_variance_norm, models.py:64-68, given stats). */
 int ast_plane_normalize_f32(const float* x, const float* mean, const float* std, float* out,
                             long long planes, long long hw, void* stream);
