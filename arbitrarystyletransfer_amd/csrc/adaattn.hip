@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
@@ -42,22 +43,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kStatThreads / 64; ++i) t += sh[i];
-  return t;
-}
+using ast_wave::block_sum;  // order A
 
 // InstanceNorm2d statistics: mean and 1/sqrt(biased var + eps) per (n, c) plane; blockIdx.y picks
 // the tensor (0 = content, 1 = style).
@@ -72,13 +58,13 @@ __global__ __launch_bounds__(kStatThreads) void in_stats_kernel(const T* __restr
   const T* __restrict__ x = (style ? s : c) + (int64_t)p * hw;
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < hw; i += kStatThreads) acc += ld(x + i);
-  const float mean = block_sum(acc, sh) / (float)hw;
+  const float mean = block_sum<kStatThreads / 64>(acc, sh) / (float)hw;
   acc = 0.f;
   for (int64_t i = threadIdx.x; i < hw; i += kStatThreads) {
     const float d = ld(x + i) - mean;
     acc += d * d;
   }
-  const float var = block_sum(acc, sh) / (float)hw;
+  const float var = block_sum<kStatThreads / 64>(acc, sh) / (float)hw;
   if (threadIdx.x == 0) {
     float* o = stats + (style ? 2 : 0) * (int64_t)planes;
     o[p] = mean;

@@ -15,21 +15,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int kT = 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+using ast_wave::wave_max;
+using ast_wave::wave_sum;
 
 // one workgroup per row: x = softmax(x) (nn.Softmax(dim=-1): exp(x - max) / sum)
 __global__ __launch_bounds__(kT) void softmax_rows_kernel(float* __restrict__ s, int cols) {

@@ -8,29 +8,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum over the 256-thread block; every thread gets the total. `sh` holds kWaves floats.
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) t += sh[i];
-  return t;
-}
+using ast_wave::block_sum;  // order A; `sh` holds kWaves floats
 
 __device__ __forceinline__ float plane_sum(const float* __restrict__ p, int64_t hw, float* sh) {
   float s = 0.f;
@@ -43,7 +28,7 @@ __device__ __forceinline__ float plane_sum(const float* __restrict__ p, int64_t 
   } else {
     for (int64_t i = threadIdx.x; i < hw; i += kThreads) s += p[i];
   }
-  return block_sum(s, sh);
+  return block_sum<kWaves>(s, sh);
 }
 
 __device__ __forceinline__ float plane_sqdev(const float* __restrict__ p, int64_t hw, float mean, float* sh) {
@@ -61,7 +46,7 @@ __device__ __forceinline__ float plane_sqdev(const float* __restrict__ p, int64_
       s += a * a;
     }
   }
-  return block_sum(s, sh);
+  return block_sum<kWaves>(s, sh);
 }
 
 // mean, std (= sqrt(var + eps)); var divides by hw - unbiased (torch: 0/0 -> NaN at hw == 1).
@@ -142,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void adain_backward_kernel(const float* _
     sg += gi;
     sgc += gi * (c[i] - mc) / sc;
   }
-  const float G = block_sum(sg, sh), GC = block_sum(sgc, sh);
+  const float G = block_sum<kWaves>(sg, sh), GC = block_sum<kWaves>(sgc, sh);
   if (dc) {
     const float gmean = G / (float)hwc, gcz = GC / (float)(hwc - 1);
     float* o = dc + p * hwc;

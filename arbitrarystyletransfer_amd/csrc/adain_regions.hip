@@ -17,6 +17,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
@@ -24,13 +25,10 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxK = AST_MAX_REGIONS;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using ast_wave::wave_sum;
 
-// Sums of KT values over the 256-thread block; every thread gets the totals. `sh` holds kWaves rows.
+// Sums of KT values over the 256-thread block (order A of wave.h, KT values at once); every thread
+// gets the totals. `sh` holds kWaves rows.
 template <int KT>
 __device__ __forceinline__ void block_sum_k(float (&v)[KT], float (*sh)[kMaxK]) {
 #pragma unroll

@@ -10,6 +10,8 @@
 //    per workgroup. Each workgroup stores its partial and takes a ticket; the workgroup that
 //    arrives last sums all partials in workgroup order and adds the total to [0]. Orders of
 //    arrival differ run to run, the summation order does not.
+// The kernels' own reductions inside a wave and a workgroup, and the three orders in which they add
+// their waves' values, are in wave.h (block_sum_fixed below is its order A with a runtime wave count).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "wave.h"
 
 namespace {
 
@@ -32,17 +33,7 @@ constexpr float kInvW = 2.5f * kBins;  // 1 / W
 
 __device__ __forceinline__ float sigm(float z) { return 1.0f / (1.0f + __expf(-z)); }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kThreads / 64; ++i) t += sh[i];
-  return t;
-}
+using ast_wave::block_sum;  // order A
 
 __device__ __forceinline__ float gs(const float* g) { return g ? *g : 1.0f; }
 
@@ -193,7 +184,7 @@ __global__ void range_loss_kernel(const float* __restrict__ x, int64_t n, float 
       dx[i] = accumulate ? dx[i] + g : g;
     }
   }
-  const float t = block_sum(s, sh);
+  const float t = block_sum<kThreads / 64>(s, sh);
   if (loss) ast_det::loss_acc_commit(loss, w_over_n * t);
 }
 
@@ -211,7 +202,7 @@ __global__ void sqdiff_kernel(const float* __restrict__ x, const float* __restri
       dx[i] = accumulate ? dx[i] + g : g;
     }
   }
-  const float t = block_sum(s, sh);
+  const float t = block_sum<kThreads / 64>(s, sh);
   if (loss) ast_det::loss_acc_commit(loss, w_over_n * t);
 }
 

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "wave.h"
 #include "x3.h"
 
 namespace {
@@ -29,13 +30,10 @@ __device__ __forceinline__ float huber(float d) {
 }
 __device__ __forceinline__ float huber_grad(float d) { return d < -1.f ? -1.f : (d > 1.f ? 1.f : d); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using ast_wave::wave_sum;
 
-// 256-thread block sum; every thread receives the total.
+// 256-thread block sum, order B of wave.h; every thread receives the total. It is block_sum_pairs in
+// value; its own copy because the four loss kernels that commit it are scheduled differently with that.
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);
   __syncthreads();

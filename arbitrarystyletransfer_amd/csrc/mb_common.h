@@ -1,9 +1,33 @@
-// Shared between mobilenet.hip (v1-v3 expand+depthwise kernels, SE, pw, launch dispatch) and
-// mb_ed4.hip (the v4 expand+depthwise kernel, compiled separately without SLP vectorisation).
+// Shared between mobilenet.hip (v1-v3 expand+depthwise kernels, SE, pw, launch dispatch),
+// mb_ed4.hip (the v4 expand+depthwise kernel, compiled separately without SLP vectorisation) and
+// mb_ed5.hip (v5).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace ast_mb {
+namespace {
+
+// Workgroup barrier for LDS hand-offs only. __syncthreads() also fences global memory, i.e. waits
+// for every outstanding global load and store of the wave (vmcnt(0)): that would drain the dw
+// kernel's output stores and the pw kernel's in-flight prefetch at every chunk.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Reflection-pad source index for i in [-(n-1), 2n-2]; clamped for out-of-tile garbage lanes.
+__device__ __forceinline__ int refl(int i, int n) {
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * n - 2 - i : i;
+  return min(max(i, 0), n - 1);
+}
+
+__device__ __forceinline__ unsigned short bf16_bits(float v) {
+  return __builtin_bit_cast(unsigned short, (__bf16)v);
+}
+
+__device__ __forceinline__ float hswish_fast(float v) {  // x * clamp(x/6 + 1/2, 0, 1): within 2 ulp of hswish
+  return v * __builtin_amdgcn_fmed3f(fmaf(v, 1.f / 6.f, 0.5f), 0.f, 1.f);
+}
+
+}  // namespace
 
 // Arguments of one expand (+BN, Hardswish) -> depthwise kxk (+BN, Hardswish) -> SE-pool launch
 // (DepthWiseConv, mobilenetv2.py:95-165, up to the SE gate).

@@ -14,19 +14,6 @@ namespace {
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Reflection-pad source index for i in [-(n-1), 2n-2]; clamped for out-of-tile garbage lanes.
-__device__ __forceinline__ int refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-  return __builtin_bit_cast(unsigned short, (bf16)v);
-}
-
 // ------------------------------------------------------------------------------------------------
 // expand + depthwise, v4 (bf16, stride 1, expand blocks): the hidden rows never leave registers
 // ------------------------------------------------------------------------------------------------
@@ -48,10 +35,6 @@ __device__ __forceinline__ unsigned short bf16_bits(float v) {
 // TH + K - 1 input rows. x is read straight from global memory (8 channels of one pixel per lane and
 // k-step; the other channel blocks of the strip read the same bytes from L2). The hidden activation
 // stays fp32 (v3 rounds it to bf16 in LDS). One wave per workgroup: no barrier but the wave's own.
-__device__ __forceinline__ float hswish_fast(float v) {  // x * clamp(x/6 + 1/2, 0, 1): within 2 ulp of hswish
-  return v * __builtin_amdgcn_fmed3f(fmaf(v, 1.f / 6.f, 0.5f), 0.f, 1.f);
-}
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 

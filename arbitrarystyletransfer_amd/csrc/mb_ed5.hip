@@ -49,24 +49,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ int refl5(int i, int n) {  // reflection pad, clamped for garbage rows / columns
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
-
-__device__ __forceinline__ unsigned short bits16(float v) { return __builtin_bit_cast(unsigned short, (bf16)v); }
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE) per pair
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-
-__device__ __forceinline__ float hswish5(float v) {  // x * clamp(x/6 + 1/2, 0, 1), as v4's hswish_fast
-  return v * __builtin_amdgcn_fmed3f(fmaf(v, 1.f / 6.f, 0.5f), 0.f, 1.f);
 }
 
 #ifndef ED5_SKIP
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(64 * NW, 2) void expand_dw5_kernel(EdArgs a, int st
 
   // x fragments of this wave's input rows j = wv + 8 t (A of the expand: lane (pixel r, k-group h))
   const int pc = 16 * ((r >> 2) & 1) + (r & 3) + 4 * (r >> 3);  // C rows of a lane half = 16 consecutive columns
-  const int gx = refl5(x0 + pc, a.w);
+  const int gx = refl(x0 + pc, a.w);
   const int hw2 = 2 * a.h * a.w;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<bf16*>(reinterpret_cast<const bf16*>(a.x1) + (int64_t)n * a.cin * (hw2 / 2)), 0, a.cin * hw2,
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(64 * NW, 2) void expand_dw5_kernel(EdArgs a, int st
   for (int t = 0; t < NT; ++t) {
     const int j = wv + NW * t;
     if (j < IR) {
-      const int vrow = 8 * h * hw2 + 2 * (refl5(y0 - P5 + j, a.h) * a.w + gx);
+      const int vrow = 8 * h * hw2 + 2 * (refl(y0 - P5 + j, a.h) * a.w + gx);
       unsigned raw[KS][8];
 #pragma unroll
       for (int q = 0; q < KS; ++q)
@@ -195,7 +181,7 @@ __global__ __launch_bounds__(64 * NW, 2) void expand_dw5_kernel(EdArgs a, int st
   };
   auto write_t = [&](int it, float v) {  // weight (ky, kx) of a channel into its 8 copies: copy k entry 7 + kx - k
     const int c = it / 25, t = it - 25 * c, ky = t / 5, kx = t - 5 * ky;
-    const unsigned short b = bits16(v);
+    const unsigned short b = bf16_bits(v);
     unsigned short* row = reinterpret_cast<unsigned short*>(Ts + c * TP + ky * 256) + 7 + kx;
 #pragma unroll
     for (int k = 0; k < 8; ++k) row[16 * k - k] = b;
@@ -231,7 +217,7 @@ __global__ __launch_bounds__(64 * NW, 2) void expand_dw5_kernel(EdArgs a, int st
       if (j < IR) {
         unsigned pk[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pk[i] = pack2(hswish5(ce[t][2 * i]), hswish5(ce[t][2 * i + 1]));
+        for (int i = 0; i < 8; ++i) pk[i] = pack2(hswish_fast(ce[t][2 * i]), hswish_fast(ce[t][2 * i + 1]));
         uint4* dst = reinterpret_cast<uint4*>(Hs + r * CP + j * RP + 32 * h);
         if (!(ED5_SKIP & 16)) {
           dst[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
@@ -269,7 +255,7 @@ __global__ __launch_bounds__(64 * NW, 2) void expand_dw5_kernel(EdArgs a, int st
       // epilogue: lane (row r, half h), registers 4 q + e = column 8 q + 4 h + e
       float y[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) y[i] = hswish5(acc[i]);
+      for (int i = 0; i < 16; ++i) y[i] = hswish_fast(acc[i]);
       float t = 0.f;
       if (!edge) {
 #pragma unroll

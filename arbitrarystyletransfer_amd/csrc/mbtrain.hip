@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "wave.h"
 #include "x3.h"
 
 namespace {
@@ -27,17 +28,7 @@ inline unsigned grid_for(int64_t n, int64_t cap = 1 << 20) {
   return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kT / 64; ++i) t += sh[i];
-  return t;
-}
+using ast_wave::block_sum;  // order A
 
 // ------------------------------------------------------------------------------------------------
 // GEMM: C[b][m][n] (+)= sum_k A[b][m][k] * B[b][k][n], general strides. 64x64 tile per workgroup,
@@ -632,8 +623,8 @@ __global__ __launch_bounds__(kT) void bn_part_stats_kernel(const float* __restri
     s1 += d;
     s2 = fmaf(d, d, s2);
   }
-  s1 = block_sum(s1, sh);
-  s2 = block_sum(s2, sh);
+  s1 = block_sum<kT / 64>(s1, sh);
+  s2 = block_sum<kT / 64>(s2, sh);
   if (threadIdx.x == 0) {
     const int S = gridDim.x * gridDim.y;
     float* o = part + ((int64_t)ch * S + (int64_t)b * gridDim.x + sx) * 3;
@@ -759,8 +750,8 @@ __global__ __launch_bounds__(kT) void bn_part_bwd_kernel(const float* __restrict
     s1 += gv;
     s2 = fmaf(gv, (xv - mu) * is, s2);
   }
-  s1 = block_sum(s1, sh);
-  s2 = block_sum(s2, sh);
+  s1 = block_sum<kT / 64>(s1, sh);
+  s2 = block_sum<kT / 64>(s2, sh);
   if (threadIdx.x == 0) {
     const int S = gridDim.x * gridDim.y;
     float* p = part + ((int64_t)ch * S + (int64_t)b * gridDim.x + sx) * 2;
@@ -922,7 +913,7 @@ __global__ __launch_bounds__(kT) void plane_dot_kernel(const float* __restrict__
       else s += ACT ? elt<0>(xp[i], 0.f) : xp[i];
     }
   }
-  const float t = block_sum(s, sh);
+  const float t = block_sum<kT / 64>(s, sh);
   if (threadIdx.x == 0) out[p] = t * scale;
 }
 

@@ -24,6 +24,7 @@
 #include "../../include/ast_hip.h"
 #include "mb_common.h"
 #include "det.h"
+#include "wave.h"
 
 namespace {
 
@@ -41,17 +42,9 @@ __device__ __forceinline__ T from_f(float v) { return (T)v; }
 // torch Hardswish: x * min(max(x + 3, 0), 6) / 6 (here * (1/6): within 1 ulp, no IEEE divide sequence)
 __device__ __forceinline__ float hswish(float v) { return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f); }
 
-// Workgroup barrier for LDS hand-offs only. __syncthreads() also fences global memory, i.e. waits
-// for every outstanding global load and store of the wave (vmcnt(0)): that would drain the dw
-// kernel's output stores and the pw kernel's in-flight prefetch at every chunk.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Reflection-pad source index for i in [-(n-1), 2n-2]; clamped for out-of-tile garbage lanes.
-__device__ __forceinline__ int refl(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
+using ast_mb::bf16_bits;  // mb_common.h (shared with mb_ed4.hip and mb_ed5.hip)
+using ast_mb::lds_barrier;
+using ast_mb::refl;
 
 // One 16x16 MFMA k-step from two row-major [row][k] LDS images (A: 16 rows from `a`, B: 16 rows from `b`).
 template <typename T>
@@ -799,10 +792,6 @@ __host__ __device__ constexpr Ed3Lds ed3_lds(int cin_pad, int hid) {
   return l;
 }
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-  return __builtin_bit_cast(unsigned short, (bf16)v);
-}
-
 // Sum over each 16-lane row by DPP (no LDS round trips): every lane ends with its row's sum.
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x) {
@@ -1484,9 +1473,8 @@ __global__ __launch_bounds__(kThreads) void dense3x3v8_kernel(const TI* __restri
 // ------------------------------------------------------------------------------------------------
 // AdaIN on bf16 maps (fp32 statistics), models.py:43-51 (+ alpha blend, models.py:471)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum256(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+__device__ __forceinline__ float block_sum256(float v, float* sh) {  // order C of wave.h: this kernel's own
+  v = ast_wave::wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();

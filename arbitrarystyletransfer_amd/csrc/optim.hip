@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
@@ -23,14 +24,7 @@ struct TensorEntry {
   long long chunk0;  // first global chunk index of this tensor
 };
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
+using ast_wave::block_sum_pairs;  // order B
 
 __device__ __forceinline__ int find_entry(const TensorEntry* t, int nt, long long chunk) {
   int lo = 0, hi = nt - 1;
@@ -53,7 +47,7 @@ __global__ void sq_norm_kernel(const TensorEntry* __restrict__ t, int nt, float*
     const float g = e.g[i];
     s += g * g;
   }
-  s = block_sum(s, sh);
+  s = block_sum_pairs(s, sh);
   if (threadIdx.x == 0) partial[chunk] = s;
 }
 
@@ -63,7 +57,7 @@ __global__ void norm_finish_kernel(const float* __restrict__ partial, long long 
   __shared__ float sh[4];
   float s = 0.f;
   for (long long i = threadIdx.x; i < nchunks; i += kThreads) s += partial[i];
-  s = block_sum(s, sh);
+  s = block_sum_pairs(s, sh);
   if (threadIdx.x == 0) {
     const float norm = sqrtf(s);
     state[0] = norm;

@@ -21,6 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "wave.h"
 
 namespace {
 
@@ -31,30 +32,9 @@ constexpr int kMaxC = 1024;
 constexpr int kMaxSplits = 8;           // covariance K splits per sample
 constexpr float kTraceFloor = 1e-20f;
 
-// Sum / max of v over the workgroup in a fixed order; every thread receives the result.
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kT / 64; ++i) t += sh[i];
-  return t;
-}
-
-__device__ __forceinline__ float block_max(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-#pragma unroll
-  for (int i = 1; i < kT / 64; ++i) t = fmaxf(t, sh[i]);
-  return t;
-}
+// Sum (order A) / max of v over the workgroup in a fixed order; every thread receives the result.
+using ast_wave::block_max;
+using ast_wave::block_sum;
 
 // ------------------------------------------------------------------------------------------------
 // One 64x64 tile of (A - amu) . (B - bmu) over k in [kbeg, kend), as this wave's 32x32 accumulator.
@@ -142,7 +122,7 @@ __global__ __launch_bounds__(kT) void wct_mean_kernel(const float* __restrict__ 
   const float x0 = p[0];
   float s = 0.f;
   for (int64_t i = threadIdx.x; i < M; i += kT) s += p[i] - x0;
-  s = block_sum(s, sh);
+  s = block_sum<kT / 64>(s, sh);
   if (threadIdx.x == 0) mean[blockIdx.x] = x0 + s / (float)M;
 }
 
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(kT) void wct_ridge_kernel(float* __restrict__ cov, 
   float* S = cov + (int64_t)blockIdx.x * C * C;
   float t = 0.f;
   for (int i = threadIdx.x; i < C; i += kT) t += S[(int64_t)i * C + i];
-  t = block_sum(t, sh);
+  t = block_sum<kT / 64>(t, sh);
   const float eps = eps_rel * fmaxf(t / (float)C, kTraceFloor);
   for (int i = threadIdx.x; i < C; i += kT) S[(int64_t)i * C + i] += eps;
 }
@@ -218,14 +198,14 @@ __global__ __launch_bounds__(kT) void wct_norm_kernel(const float* __restrict__ 
   const float* S = cov + (int64_t)blockIdx.x * cc;
   float m = 0.f;
   for (int64_t i = threadIdx.x; i < cc; i += kT) m = fmaxf(m, fabsf(S[i]));
-  m = block_max(m, sh);
+  m = block_max<kT / 64>(m, sh);
   __syncthreads();
   float s = 0.f;
   for (int64_t i = threadIdx.x; i < cc; i += kT) {
     const float v = S[i] / m;
     s += v * v;
   }
-  s = block_sum(s, sh);
+  s = block_sum<kT / 64>(s, sh);
   if (threadIdx.x == 0) norm[blockIdx.x] = m * sqrtf(s);
 }
 
@@ -431,7 +411,7 @@ __global__ __launch_bounds__(kT) void wct_region_mean_kernel(const float* __rest
   const float x0 = p[idx[0]];
   float s = 0.f;
   for (int i = threadIdx.x; i < mk; i += kT) s += p[idx[i]] - x0;
-  s = block_sum(s, sh);
+  s = block_sum<kT / 64>(s, sh);
   if (threadIdx.x == 0) *out = x0 + s / (float)mk;
 }
 
@@ -504,7 +484,7 @@ __global__ __launch_bounds__(kT) void wct_region_ridge_kernel(float* __restrict_
   float* S = cov + (int64_t)blockIdx.x * C * C;
   float t = 0.f;
   for (int i = threadIdx.x; i < C; i += kT) t += S[(int64_t)i * C + i];
-  t = block_sum(t, sh);
+  t = block_sum<kT / 64>(t, sh);
   const float eps = eps_rel * fmaxf(t / (float)C, kTraceFloor);
   for (int i = threadIdx.x; i < C; i += kT) S[(int64_t)i * C + i] += eps;
 }
