@@ -50,6 +50,9 @@ SIGNATURES = {
     "ast_efdm_ex_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _ll, _p]),
     "ast_plane_sort_workspace_bytes": (_ll, [_ll, _ll, _i, _i]),
     "ast_plane_sort_f32": (_i, [_p, _p, _p, _ll, _ll, _i, _p, _ll, _p]),
+    "ast_efdm_region_sort_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ast_efdm_regions_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "ast_efdm_regions_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
     "ast_wct_default_iters": (_i, [_i, _f]),
     "ast_wct_cov_workspace_bytes": (_ll, [_i, _i, _ll]),
     "ast_wct_cov_f32": (_i, [_p, _p, _p, _i, _i, _ll, _f, _p, _ll, _p]),

@@ -35,6 +35,7 @@ region_stats            -- (masked per-region channel statistics)    --
 adain_regions           -- (regional multi-style AdaIN)              --
 efdm                    -- (exact feature distribution matching)     d content = grad (straight-through)
 plane_sort              -- (segmented totalOrder sort of planes)     --
+efdm_regions            -- (EFDM per region, mix of a style bank)    raises NotImplementedError
 wct                     -- (whitening and colouring transform)       raises NotImplementedError
 wct_regions             -- (WCT per region, mix of a style bank)     raises NotImplementedError
 style_swap              -- (patch-matching style swap)               raises NotImplementedError
@@ -727,6 +728,26 @@ def _(x):
     return torch.empty_like(x), x.new_empty(x.shape, dtype=torch.int32)
 
 
+@custom_op("ast_hip::efdm_regions", mutates_args=())
+def efdm_regions(content: Tensor, labels: Tensor, styles: Tensor, mix: Tensor, style_labels: Optional[Tensor],
+                 alpha: float) -> Tensor:
+    """EFDM per region of a uint8 label map towards a per-region mix [N or 1, K, S] of a bank of styles."""
+    return ops.efdm_regions(content, labels, styles, mix, style_labels=style_labels, alpha=alpha)
+
+
+@register_fake("ast_hip::efdm_regions")
+def _(content, labels, styles, mix, style_labels, alpha):
+    return torch.empty_like(content)
+
+
+def _efdm_regions_backward(ctx, g):
+    raise NotImplementedError("ast_hip::efdm_regions has no backward: regional distribution matching is "
+                              "inference-only")
+
+
+register_autograd("ast_hip::efdm_regions", _efdm_regions_backward)
+
+
 # ------------------------------------------------------------------------------------------------
 # Whitening and colouring transform (csrc/wct.hip; inference only)
 # ------------------------------------------------------------------------------------------------
@@ -866,5 +887,5 @@ def _(labels, regions, passes):
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
                   "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
-                  "region_stats", "adain_regions", "efdm", "plane_sort", "wct", "wct_regions", "style_swap",
-                  "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]
+                  "region_stats", "adain_regions", "efdm", "plane_sort", "efdm_regions", "wct", "wct_regions",
+                  "style_swap", "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]

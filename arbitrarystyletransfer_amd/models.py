@@ -524,8 +524,10 @@ class AdaINStyleTransfer(nn.Module):
     `stylize_swap` stylises by style swap (patch matching on the relu4_1 maps) with the same
     encoder and decoder, whatever the transform; `stylize_swap_regions` is its guided form over a
     bank of styles, steered by the label maps of `stylize_regions`. `stylize_regions_wct` is
-    `stylize_regions` with WCT per region (ops.wct_regions), also whatever the transform.
-    The three regional methods take `labels=AutoRegions(k)` in place of label maps: the maps, the
+    `stylize_regions` with WCT per region (ops.wct_regions), also whatever the transform, and
+    `stylize_regions_efdm` the same with EFDM per region (ops.efdm_regions): the regional method of
+    a model trained with transform="efdm".
+    The four regional methods take `labels=AutoRegions(k)` in place of label maps: the maps, the
     style maps and the weights then come from a k-means over the style features (`auto_labels`).
     """
 
@@ -543,8 +545,10 @@ class AdaINStyleTransfer(nn.Module):
 
     def _needs_statistics(self, what):
         if self.transform != "adain":
+            other = ("; stylize_regions_efdm and stylize_regions_wct take the same arguments whatever the transform"
+                     if what == "stylize_regions" else "")
             raise NotImplementedError(f"{what} works on per-channel mean and std, which transform="
-                                      f"{self.transform!r} does not use; build the model with transform='adain'")
+                                      f"{self.transform!r} does not use; build the model with transform='adain'{other}")
 
     def encode_pair(self, content_img, style_img):
         if content_img.shape[1:] == style_img.shape[1:]:
@@ -597,7 +601,7 @@ class AdaINStyleTransfer(nn.Module):
         """The region maps that `labels=auto` gives the regional methods, for content_img [N, 3, H, W]
         and the style bank style_imgs [S, 3, Hs, Ws]: (labels uint8 [N, h, w], style_labels uint8
         [S, hs, ws], weights float64 CPU [K, S]) at relu4_1 resolution, in the form stylize_regions,
-        stylize_regions_wct and stylize_swap_regions take. The bank's features are clustered together
+        stylize_regions_wct, stylize_regions_efdm and stylize_swap_regions take. The bank's features are clustered together
         (see AutoRegions), so region k is the same sub-style in every map. weights[k, s] is the number
         of pixels of region k in style s after smoothing, 0 below two pixels; a region with no style
         pixels left is relabelled 255 in both maps (its content passes through, its style pixels
@@ -799,6 +803,53 @@ class AdaINStyleTransfer(nn.Module):
             t = _ops().wct_regions(f_c, lab, f_s, mix, sl, float(alpha), float(eps_rel), int(iters))
         else:
             t = ops.wct_regions(f_c, lab, f_s, mix, style_labels=sl, alpha=alpha, eps_rel=eps_rel, iters=iters)
+        out = self.decoder(t)
+        if preserve_color:
+            return _luma_transfer(out, content_img)
+        return out
+
+    def stylize_regions_efdm(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
+                             style_labels=None, preserve_color: bool = False):
+        """stylize_regions with exact feature distribution matching (ops.efdm_regions on the relu4_1
+        maps) in AdaIN's place: in region k the pixel of rank r among the region's own pixels takes
+        the weights[k]-mix of the styles' sorted values at the matching quantile, channel by channel
+        the Wasserstein barycentre of the styles' distributions. Inference only, whatever `transform`
+        the model was built with; it is the regional method of a model trained with transform="efdm".
+
+        content_img, style_imgs, labels, weights, style_labels, alpha and preserve_color as in
+        stylize_regions (labels=None: one region, plain style interpolation; weights=None: region k
+        takes style k, or equal weights when labels is None). With style_labels region k takes the
+        values of each style's own region k; where a style of non-zero weight has no such pixel, the
+        region keeps the content's features. relu4_1 maps of at most ops.EFDM_FUSED_MAX pixels (a
+        1024 x 1024 image). labels=AutoRegions(...) as in stylize_regions."""
+        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("stylize_regions_efdm is inference-only; run it under torch.no_grad()")
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError("stylize_regions_efdm needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        auto = self._auto_request(labels, style_labels, weights)
+        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
+        if s > ops.MAX_STYLE_ROWS:
+            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
+        if auto is None:
+            w = region_weights(weights, n, s, single_region=labels is None)
+        f_c = self.encoder(content_img)[0]
+        f_s = self.encoder(style_imgs)[0]
+        if auto is not None:
+            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
+            w = region_weights(weights, n, s)
+        if labels is None:
+            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
+        else:
+            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(f_c.device)
+        sl = None
+        if style_labels is not None:
+            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(f_c.device)
+        mix = w.float().to(f_c.device)
+        if _compiling():
+            t = _ops().efdm_regions(f_c, lab, f_s, mix, sl, float(alpha))
+        else:
+            t = ops.efdm_regions(f_c, lab, f_s, mix, style_labels=sl, alpha=alpha)
         out = self.decoder(t)
         if preserve_color:
             return _luma_transfer(out, content_img)

@@ -639,6 +639,62 @@ def wct_regions(content: torch.Tensor, labels: torch.Tensor, styles: torch.Tenso
     return out
 
 
+# Regional EFDM (csrc/efdm_regions.hip): distribution matching per region, towards a mix of a style bank
+
+def efdm_region_sort(x: torch.Tensor, labels: torch.Tensor, regions: int):
+    """The bank stage of efdm_regions: every plane of x [S, C, H, W] ordered by (min(label, regions),
+    totalOrder key, index) -- region after region, each ascending, the pixels labelled >= regions
+    last -- as (sorted [S, C, H*W], count [S, regions] int32). labels uint8 [S, H, W], or None: one
+    region holds everything (the plain sort; count[:, 0] = H*W). Planes of at most EFDM_FUSED_MAX."""
+    regions = _regions(regions)
+    if labels is None:
+        x = _dev(x, "x")
+        if x.dim() != 4 or x.numel() == 0:
+            raise HipOpError(f"x must be a non-empty NCHW map, got {tuple(x.shape)}")
+        s, c, h, w = (int(d) for d in x.shape)
+    else:
+        x, labels, s, c, h, w = _map_and_labels(x, labels, "x")
+    vals = torch.empty((s, c, h * w), device=x.device, dtype=torch.float32)
+    count = torch.empty((s, regions), device=x.device, dtype=torch.int32)
+    check(_timed(f"efdm_region_sort {c}ch {h}x{w} K{regions}", -8 * x.numel(), x.device,
+                 lambda: lib().ast_efdm_region_sort_f32(ptr(x), ptr(labels), ptr(vals), ptr(count), s, c, h, w, regions,
+                                                        stream_ptr(x.device))), "efdm_region_sort")
+    return vals, count
+
+
+def efdm_regions(content: torch.Tensor, labels: torch.Tensor, styles: torch.Tensor, mix: torch.Tensor,
+                 style_labels: torch.Tensor = None, alpha: float = 1.0):
+    """Regional EFDM: in region k of sample n (the pixels with labels[n] == k) the pixel of rank r among
+    the region's Mc_k pixels takes sum_s mix[n, k, s] * S_sk[((2r + 1) * Ms_sk) // (2 * Mc_k)], S_sk the
+    sorted values of style s's plane [S, C, Hs, Ws] (shared by the batch) or, with style_labels
+    [S, Hs, Ws], of its own region k: per channel the Wasserstein barycentre of the styles'
+    distributions. Pixels labelled >= K, and regions whose class a used style lacks, pass through bit
+    for bit. mix is [K, S], [1, K, S] or [N, K, S] on the device, non-negative; a style of weight
+    exactly 0 is never used, and a one-hot row copies style values (no arithmetic at alpha == 1).
+    alpha as efdm. Planes of at most EFDM_FUSED_MAX elements."""
+    content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
+    styles = _dev(styles, "styles")
+    if styles.dim() != 4 or styles.numel() == 0 or styles.shape[1] != c or styles.device != content.device:
+        raise HipOpError(f"efdm_regions needs a non-empty style bank [S, C={c}, Hs, Ws] on {content.device}, got "
+                         f"{tuple(styles.shape)} on {styles.device}")
+    s, hs, ws = int(styles.shape[0]), int(styles.shape[2]), int(styles.shape[3])
+    mix, k = _region_mix(mix, n, s, content.device, "efdm_regions")
+    if style_labels is not None:
+        style_labels = _labels(style_labels, "style_labels")
+        if tuple(style_labels.shape) != (s, hs, ws) or style_labels.device != content.device:
+            raise HipOpError(f"style_labels must be [S, Hs, Ws] = {(s, hs, ws)} on {content.device}, got "
+                             f"{tuple(style_labels.shape)} on {style_labels.device}")
+    L = lib()
+    nbytes = int(L.ast_efdm_regions_workspace_bytes(n, c, h, w, k, s, hs, ws))
+    wsb = _ws_bytes(nbytes, "efdm_regions workspace", content.device)
+    out = torch.empty_like(content)
+    algo = 4 * (2 * content.numel() + 2 * styles.numel()) + labels.numel()   # algorithmic: c, out, the bank in and out
+    check(_timed(f"efdm_regions {c}ch {h}x{w} K{k} S{s}", -algo, content.device, lambda: L.ast_efdm_regions_f32(
+        ptr(content), ptr(labels), ptr(styles), ptr(style_labels), ptr(mix), ptr(out), n, c, h, w, k, s, hs, ws,
+        int(mix.shape[0]), float(alpha), ptr(wsb), nbytes, stream_ptr(content.device))), "efdm_regions")
+    return out
+
+
 # Style swap (csrc/swap.hip): the limits of ast_hip.h
 SWAP_MAX_C = 1024
 

@@ -216,6 +216,56 @@ int ast_plane_sort_f32(const float* x, float* sorted, int* index_or_null, long l
                        long long m, int chunk, void* workspace, long long workspace_bytes,
                        void* stream);
 
+/* Regional EFDM (csrc/efdm_regions.hip; an extension, no reference counterpart): the matching above
+ * per region of a label map, towards a per-region mix of a bank of styles. Order, keys and ties are
+ * those of ast_efdm_f32.
+ * Inputs: content c [n, ch, h, w] fp32; labels uint8 [n, h, w], shared by the channels of a sample;
+ * K = regions in 1..AST_MAX_REGIONS: label k < K puts the pixel in region k, any label >= K (255 by
+ * convention) passes it through. Styles [S, ch, hs, ws] shared by the batch, S in
+ * 1..AST_MAX_STYLE_ROWS, optionally with style_labels uint8 [S, hs, ws]. mix fp32 [n or 1, K, S] on
+ * the device, non-negative (the caller normalises the rows). Mc = h*w and Ms = hs*ws are at most
+ * AST_EFDM_FUSED_MAX: a larger plane gives AST_E_UNSUPPORTED (the chunk-and-merge path of
+ * ast_efdm_f32 has no regional form).
+ * Rule, for sample b, channel and region k: I_k = the pixels with labels[b] == k, Mc_k their number,
+ * r(i) the stable ascending rank of pixel i among I_k only. For style s, J_(s,k) = all its pixels or,
+ * with style_labels, those with style_labels[s] == k; Ms_(s,k) their number; S_(s,k) the plane's
+ * values on J_(s,k) in ascending order. t_s[i] = S_(s,k)[((2 r(i) + 1) * Ms_(s,k)) / (2 * Mc_k)] and
+ * t[i] = sum_s mix[b, k, s] * t_s[i] in fp32 in ascending s (fp32 products, fp32 sums, nothing fused):
+ * the 1-D Wasserstein barycentre of the styles' distributions. A weight of exactly 0 is skipped and its
+ * style's values never reach the result (they may be NaN); when exactly one weight of the row is
+ * non-zero, t[i] is that t_s[i] bit for bit, with no multiply; a row of zeros gives the empty sum, 0.
+ *   out[i] = t[i]                           when alpha == 1,
+ *   out[i] = c[i] + alpha * (t[i] - c[i])   otherwise, in fp32.
+ * Pass-through, out = c bit for bit whatever alpha: where label >= K; in a region k for which a style
+ * of non-zero weight has Ms_(s,k) == 0 (the rule of regional WCT). A non-finite value stays inside
+ * its own region's ranking.
+ * One region, one style and no style_labels is ast_efdm_f32 with ns = 1, bit for bit at alpha == 1.
+ * Every plane is sorted once whatever K and S: the bank by one launch shared by the batch, the
+ * content inside the apply launch; the rank inside a region is the count of earlier sorted positions
+ * with the same label. No atomics, no host synchronisation, no allocation: bitwise reproducible; no
+ * launch parameter depends on the contents of a label map, so a captured graph replays with other
+ * labels. workspace: device memory, 4-byte aligned (AST_E_UNSUPPORTED otherwise), at least
+ * ast_efdm_regions_workspace_bytes; it holds the sorted bank.
+ * AST_E_NULLPTR: a null pointer (but the optional one). AST_E_SHAPE: a size <= 0, regions or S out of
+ * range, a mix batch outside {1, n}, more than 2^31 - 1 planes, a short workspace. The query returns
+ * the same negative codes. All checks run before the first launch. */
+
+/* The bank stage on its own: every plane of x [s, c, h, w] in the order (min(label, K), key, index) --
+ * region after region, each ascending, the pixels labelled >= K last -- as `sorted` [s, c, h*w], and
+ * count [s, K] (int32), the pixels of every region. labels_or_null uint8 [s, h, w]; NULL: one region
+ * holds everything (the plain ascending sort, count[:, 0] = h*w and 0 elsewhere). Any s >= 1. */
+int ast_efdm_region_sort_f32(const float* x, const unsigned char* labels_or_null, float* sorted,
+                             int* count, int s, int c, int h, int w, int regions, void* stream);
+
+/* The whole op: the bank sort into the workspace, then one launch over the content planes. */
+long long ast_efdm_regions_workspace_bytes(int n, int c, int hc, int wc, int regions, int styles,
+                                           int hs, int ws);
+int ast_efdm_regions_f32(const float* content, const unsigned char* labels, const float* styles,
+                         const unsigned char* style_labels_or_null, const float* mix, float* out,
+                         int n, int c, int hc, int wc, int regions, int styles_n, int hs, int ws,
+                         int mix_n, double alpha, void* workspace, long long workspace_bytes,
+                         void* stream);
+
 /* Whitening and colouring transform (WCT, Li et al. NeurIPS 2017; csrc/wct.hip; an extension, no
  * reference counterpart): the feature transform that matches the cross-channel covariance.
  * content x [n, c, hc, wc], style s [ns, c, hs, ws] with ns == n, or ns == 1 (one style shared by the
