@@ -306,7 +306,9 @@ __global__ __launch_bounds__(WM * 64, OCC) void conv3x3_x3_kernel(ConvArgs a) {
       // tap, the tap's B fragments) are read while step s's MFMAs run. The stamps showed the wave
       // that finishes a chunk last, alone on its SIMD, issuing MFMAs at ~70% of the pipe rate: each
       // step waited on reads issued just before it (profiles/r05_x3_stamps.txt). Same products in
-      // the same order per accumulator as the round-4 loop: bit-identical.
+      // the same order per accumulator as the round-4 loop: bit-identical. A step opens with an MFMA
+      // and its reads follow, one per MFMA: with a read first, every step began by waiting
+      // (lgkmcnt(0)) for a read issued one instruction earlier (profiles/r10_x3_step_boundaries.txt).
       constexpr int NSTEP = 9 * RM;
       bf16x8 gb[2][3][Q];  // B fragments (g1, g2, g3) of a tap, by tap parity
       bf16x8 fa[2][2][2];  // A fragments (f1, f2) x pixel tile of a step, by step parity
@@ -358,10 +360,12 @@ __global__ __launch_bounds__(WM * 64, OCC) void conv3x3_x3_kernel(ConvArgs a) {
         if (st + 1 < NSTEP) {
           X3P_READ_A(sb ^ 1, st + 1);
           nrd = 4;
-          if ((st + 1) % RM == 0) {
-            X3P_READ_B(tb ^ 1, (st + 1) / RM);
-            nrd += 3 * Q;
-          }
+        }
+        // (an `if` of its own: nested in the one above, the compiler put reads next to the step's
+        // boundary wait again in 6 of the 16 instantiations, profiles/r10_x3_step_boundaries.txt)
+        if (st + 1 < NSTEP && (st + 1) % RM == 0) {
+          X3P_READ_B(tb ^ 1, (st + 1) / RM);
+          nrd += 3 * Q;
         }
         // the three products of an accumulator in the same order, but product-major: 2Q
         // independent MFMAs separate each from the next one on the same accumulator
@@ -380,11 +384,13 @@ __global__ __launch_bounds__(WM * 64, OCC) void conv3x3_x3_kernel(ConvArgs a) {
 #pragma unroll
           for (int q = 0; q < Q; ++q)
             acc16[i][pt][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[sb][0][pt], gb[tb][0][q], acc16[i][pt][q], 0, 0, 0);
-        // one LDS read per MFMA while the next step's reads last, then the rest of the MFMAs
+        // an MFMA opens the step, then one LDS read per MFMA while the next step's reads last, then
+        // the rest of the MFMAs: the wait for this step's operands, which the compiler puts ahead of
+        // the step's first MFMA, then covers no read issued after the previous step's MFMAs
 #pragma unroll
         for (int r = 0; r < nrd; ++r) {
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
         if (nrd == 4) __builtin_amdgcn_sched_group_barrier(0x008, 6 * Q - 4, 0);
         else if (nrd == 4 + 3 * Q) __builtin_amdgcn_sched_group_barrier(0x008, 3 * Q - 4, 0);
