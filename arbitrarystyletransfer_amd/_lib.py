@@ -81,7 +81,15 @@ SIGNATURES = {
     "ast_patch_gather_guided_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ast_style_swap_guided_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "ast_style_swap_guided_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p]),
-    "ast_kmeans_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_cosine_norms_f32": (_i, [_p, _p, _i, _i, _i, _p]),
+    "ast_cosine_match_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_cosine_match_f32": (_i, [_p] * 8 + [_i] * 6 + [_p, _ll, _p]),
+    "ast_remd_means_f32": (_i, [_p] * 6 + [_i, _i, _i, _f, _i, _p]),
+    "ast_remd_loss_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "ast_remd_loss_f32": (_i, [_p] * 12 + [_i] * 5 + [_f, _i, _p, _ll, _p]),
+    "ast_remd_loss_backward_workspace_bytes": (_ll, [_i, _i, _i]),
+    "ast_remd_loss_backward_f32": (_i, [_p] * 11 + [_i] * 5 + [_f, _p, _ll, _p]),
+    "ast_kmeans_workspace_bytes":(_ll, [_i, _i, _i, _i, _i]),
     "ast_kmeans_seed_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "ast_kmeans_assign_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ast_kmeans_update_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),

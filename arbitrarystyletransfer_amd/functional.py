@@ -697,6 +697,25 @@ class HistLossFn(torch.autograd.Function):
         return dx, None, None
 
 
+class RemdLossFn(torch.autograd.Function):
+    """weight * the relaxed earth mover's distance between the pixels of x and of y (ops.remd_loss); y
+    is data (no gradient). _branch as in ops.remd_loss."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, _branch=0):
+        x, y = _dev(x, "t_cs_map"), _dev(y, "style_map")
+        loss, _, _, branch, state = ops.remd_loss(x, y, float(weight), int(_branch), acc=_acc(x))
+        ctx.save_for_backward(x, y, branch, *state)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, branch, *state = ctx.saved_tensors
+        dx = ops.remd_loss_backward(x, y, tuple(state), branch, _dev(g, "grad"), ctx.weight)
+        return dx, None, None, None
+
+
 class RangeLossFn(torch.autograd.Function):
     """weight * compute_content_loss(x, torch.clip(x.detach(), 0, 1)) (train.py:259)."""
 

@@ -21,6 +21,7 @@ style_loss              losses.py:128-139                            d x
 huber_loss              losses.py:124-126 (compute_content_loss)     d x, d y
 tv_loss                 losses.py:90-103                             d img
 hist_loss               losses.py:84-87 (SingleDimHist + EMD)        d x
+remd_loss               -- (relaxed EMD: two-way cosine match)       d x
 range_loss              train.py:259                                 d x
 sqdiff_mean             train.py:268                                 d x
 mb_expand_dw            mobilenetv2.py:153-161 (to the SE pool)      -- (eval BN folded: inference)
@@ -438,6 +439,37 @@ def _hist_backward(ctx, g, *_):
 
 
 register_autograd("ast_hip::hist_loss", _hist_backward, setup_context=_hist_setup)
+
+
+@custom_op("ast_hip::remd_loss", mutates_args=())
+def remd_loss(x: Tensor, y: Tensor, weight: float, branch: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor,
+                                                                         Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """weight * the relaxed earth mover's distance of ops.remd_loss (branch: its _branch); outputs (loss,
+    row_mean, col_mean, branch, inv_x, inv_y, row_min, row_index, col_min, col_index)."""
+    loss, rmean, cmean, br, state = ops.remd_loss(x, y, float(weight), int(branch), acc=_acc(x))
+    return (loss, rmean, cmean, br) + tuple(state)
+
+
+@register_fake("ast_hip::remd_loss")
+def _(x, y, weight, branch):
+    n, (h, w), (hs, ws) = x.shape[0], x.shape[2:], y.shape[2:]
+    i32 = dict(dtype=torch.int32)
+    return (x.new_empty(()), x.new_empty((n,)), x.new_empty((n,)), x.new_empty((n,), dtype=torch.uint8),
+            x.new_empty((n, h, w)), x.new_empty((y.shape[0], hs, ws)), x.new_empty((n, h, w)),
+            x.new_empty((n, h, w), **i32), x.new_empty((n, hs, ws)), x.new_empty((n, hs, ws), **i32))
+
+
+def _remd_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], *output[3:])
+    ctx.weight = float(inputs[2])
+
+
+def _remd_backward(ctx, g, *_):
+    x, y, branch, *state = ctx.saved_tensors
+    return ops.remd_loss_backward(x, y, tuple(state), branch, g.contiguous(), ctx.weight), None, None, None
+
+
+register_autograd("ast_hip::remd_loss", _remd_backward, setup_context=_remd_setup)
 
 
 @custom_op("ast_hip::range_loss", mutates_args=())
@@ -885,7 +917,7 @@ def _(labels, regions, passes):
 
 
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
-                  "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
+                  "remd_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
                   "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
                   "region_stats", "adain_regions", "efdm", "plane_sort", "efdm_regions", "wct", "wct_regions",
                   "style_swap", "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]

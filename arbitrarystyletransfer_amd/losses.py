@@ -62,7 +62,7 @@ __all__ = ["gram_matrix", "compute_content_loss", "compute_style_loss", "tv_loss
            "content_mvn_loss", "style_loss_weighted", "content_style_loss", "EarthMoversDistanceLoss",
            "HistLayerBase",
            "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss",
-           "compute_efdm_loss"]
+           "compute_efdm_loss", "compute_remd_loss"]
 
 
 def gram_matrix(tensor):
@@ -165,6 +165,16 @@ def compute_efdm_loss(t_cs_map, style_map, weight: float = 1.0):
     with torch.no_grad():
         target = Fn.EFDMFn.apply(x, y, 1.0)
     return Fn.SqDiffMeanFn.apply(x, target, float(weight))
+
+
+def compute_remd_loss(t_cs_map, style_map, weight: float = 1.0):
+    """The relaxed earth mover's distance style loss of one loss tap (Kolkin et al., STROTSS, CVPR 2019),
+    exact rather than sampled: with D the cosine distance between every pixel of t_cs_map [N, C, H, W]
+    and every pixel of style_map [N or 1, C, Hs, Ws] (any size), weight * mean over the batch of
+    max(mean_i min_j D, mean_j min_i D). The style map is detached; the gradient reaches t_cs_map
+    through the HIP gather backward (torch.ops.ast_hip.remd_loss)."""
+    x, y = _dev(t_cs_map, "t_cs_map"), _dev(style_map.detach(), "style_map")
+    return _ops.remd_loss(x, y, float(weight), 0)[0]
 
 
 def out_of_range_loss(img, weight: float = 1e8):

@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from ._lib import HipOpError, check, lib, ptr, stream_ptr
+from ._lib import HipOpError, check, lib, loss_accumulator, ptr, stream_ptr
 
 PAD_MODES = {"zeros": 0, "reflect": 1}
 
@@ -771,6 +771,139 @@ def style_swap(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, n
         ptr(ck), ptr(sk), ptr(s_), ptr(c_), ptr(out), ptr(index), None, n, ns, c, hc, wc, hs, ws, float(alpha),
         ptr(wsb), nbytes, stream_ptr(c_.device))), "style_swap")
     return (out, index) if return_index else out
+
+
+# Relaxed EMD style loss (csrc/remd.hip): the limits of ast_hip.h
+REMD_MAX_C = 1024
+REMD_MAX_PIXELS = 1 << 22
+REMD_ROW, REMD_COL = 1, 2   # the values of `branch`
+
+
+def _remd_pair(x: torch.Tensor, y: torch.Tensor, what: str):
+    """Two fp32 device NCHW maps with equal C and y's batch equal to x's or 1, inside the limits of
+    csrc/remd.hip: (x, y, n, ns, c, m, p) with m, p the pixel counts."""
+    x, y = _dev(x, "x"), _dev(y, "y")
+    if (x.dim() != 4 or y.dim() != 4 or x.shape[1] != y.shape[1] or y.shape[0] not in (1, x.shape[0])
+            or x.numel() == 0 or y.numel() == 0):
+        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C and a style batch of N or 1: "
+                         f"x {tuple(x.shape)} vs y {tuple(y.shape)}")
+    if x.device != y.device:
+        raise HipOpError(f"y is on {y.device}, x on {x.device}")
+    n, c = int(x.shape[0]), int(x.shape[1])
+    m, p = int(x.shape[2] * x.shape[3]), int(y.shape[2] * y.shape[3])
+    if c > REMD_MAX_C or max(m, p) > REMD_MAX_PIXELS or n > 65535:
+        raise HipOpError(f"{what}: C is at most {REMD_MAX_C}, a map has at most {REMD_MAX_PIXELS} pixels and a batch "
+                         f"65535 samples: x {tuple(x.shape)} vs y {tuple(y.shape)}")
+    return x, y, n, int(y.shape[0]), c, m, p
+
+
+def cosine_norms(x: torch.Tensor) -> torch.Tensor:
+    """1 / ||x[n, :, h, w]||_2 for every pixel of x [N, C, H, W]: [N, H, W], exactly 0 at a zero vector.
+    Equal vectors have equal inverse norms in bits."""
+    x = _dev(x, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise HipOpError(f"cosine_norms needs a non-empty NCHW map, got {tuple(x.shape)}")
+    n, c, h, w = (int(s) for s in x.shape)
+    inv = torch.empty((n, h, w), device=x.device, dtype=torch.float32)
+    check(lib().ast_cosine_norms_f32(ptr(x), ptr(inv), n, c, h * w, stream_ptr(x.device)), "cosine_norms")
+    return inv
+
+
+def cosine_match(x: torch.Tensor, y: torch.Tensor, _splits: int = 0):
+    """The two-way nearest-neighbour match in cosine distance D(i, j) = 1 - <x_i, y_j> / (|x_i| |y_j|)
+    between the pixels of x [N, C, H, W] and y [N or 1, C, Hs, Ws]: (row_min [N, H, W], row_index int32
+    [N, H, W], col_min [N, Hs, Ws], col_index int32 [N, Hs, Ws]); the lowest index on equal distances,
+    a NaN never wins, a zero vector is at distance 1 from everything. The distances are never stored.
+    _splits forces the number of workgroups that share the style pixels (0: the library's choice)."""
+    x, y, n, ns, c, m, p = _remd_pair(x, y, "cosine_match")
+    L, dev, st = lib(), x.device, stream_ptr(x.device)
+    u, v = cosine_norms(x), cosine_norms(y)
+    nb = int(L.ast_cosine_match_workspace_bytes(n, ns, m, p, int(_splits)))
+    wsb = _ws_bytes(nb, "cosine_match workspace", dev)
+    (h, w), (hs, ws) = x.shape[2:], y.shape[2:]
+    rmin = torch.empty((n, h, w), device=dev, dtype=torch.float32)
+    ridx = torch.empty((n, h, w), device=dev, dtype=torch.int32)
+    cmin = torch.empty((n, hs, ws), device=dev, dtype=torch.float32)
+    cidx = torch.empty((n, hs, ws), device=dev, dtype=torch.int32)
+    check(_timed(f"cosine_match {c}ch {m} vs {p}", 2 * n * m * p * c, dev, lambda: L.ast_cosine_match_f32(
+        ptr(x), ptr(y), ptr(u), ptr(v), ptr(rmin), ptr(ridx), ptr(cmin), ptr(cidx), n, ns, c, m, p, int(_splits),
+        ptr(wsb), nb, st)), "cosine_match")
+    return rmin, ridx, cmin, cidx
+
+
+def remd_means(row_min: torch.Tensor, col_min: torch.Tensor, weight: float = 1.0, _branch: int = 0, acc=None):
+    """(loss, row_mean [N], col_mean [N], branch uint8 [N]) from the minima of cosine_match: the last
+    stage of remd_loss. `acc`: the loss accumulator the value is added into (a fresh one if None)."""
+    if (row_min.device.type != "cuda" or row_min.dtype != torch.float32 or col_min.dtype != torch.float32
+            or row_min.device != col_min.device or row_min.shape[0] != col_min.shape[0] or row_min.numel() == 0
+            or col_min.numel() == 0):
+        raise HipOpError("remd_means needs the float32 device minima [N, ...] of cosine_match")
+    row_min, col_min = row_min.contiguous(), col_min.contiguous()
+    n, dev = int(row_min.shape[0]), row_min.device
+    rmean = torch.empty((n,), device=dev, dtype=torch.float32)
+    cmean = torch.empty((n,), device=dev, dtype=torch.float32)
+    branch = torch.empty((n,), device=dev, dtype=torch.uint8)
+    acc = loss_accumulator(dev) if acc is None else acc
+    check(lib().ast_remd_means_f32(ptr(row_min), ptr(col_min), ptr(rmean), ptr(cmean), ptr(branch), ptr(acc), n,
+                                   row_min.numel() // n, col_min.numel() // n, float(weight), int(_branch),
+                                   stream_ptr(dev)), "remd_means")
+    return acc[0], rmean, cmean, branch
+
+
+def remd_loss(x: torch.Tensor, y: torch.Tensor, weight: float = 1.0, _branch: int = 0, acc=None):
+    """The relaxed earth mover's distance style loss (Kolkin et al., CVPR 2019), exact: with r, c the row
+    and column minima of cosine_match(x, y), weight * mean over the batch of max(mean r, mean c) per
+    sample. Returns (loss, row_mean [N], col_mean [N], branch uint8 [N], state): branch is REMD_ROW where
+    mean r >= mean c, else REMD_COL; state = (inv_x, inv_y, row_min, row_index, col_min, col_index) is what
+    remd_loss_backward reads. _branch (tests): 1 / 2 takes the row / column branch for every sample."""
+    x, y, n, ns, c, m, p = _remd_pair(x, y, "remd_loss")
+    if _branch not in (0, 1, 2):
+        raise HipOpError(f"remd_loss: _branch is 0, 1 or 2, got {_branch}")
+    L, dev = lib(), x.device
+    nb = int(L.ast_remd_loss_workspace_bytes(n, ns, m, p))
+    wsb = _ws_bytes(nb, "remd_loss workspace", dev)
+    (h, w), (hs, ws) = x.shape[2:], y.shape[2:]
+    f32 = dict(device=dev, dtype=torch.float32)
+    u, v = torch.empty((n, h, w), **f32), torch.empty((ns, hs, ws), **f32)
+    rmin, cmin = torch.empty((n, h, w), **f32), torch.empty((n, hs, ws), **f32)
+    ridx = torch.empty((n, h, w), device=dev, dtype=torch.int32)
+    cidx = torch.empty((n, hs, ws), device=dev, dtype=torch.int32)
+    rmean, cmean = torch.empty((n,), **f32), torch.empty((n,), **f32)
+    branch = torch.empty((n,), device=dev, dtype=torch.uint8)
+    acc = loss_accumulator(dev) if acc is None else acc
+    check(_timed(f"remd_loss {c}ch {m} vs {p}", 2 * n * m * p * c, dev, lambda: L.ast_remd_loss_f32(
+        ptr(x), ptr(y), ptr(u), ptr(v), ptr(rmin), ptr(ridx), ptr(cmin), ptr(cidx), ptr(rmean), ptr(cmean),
+        ptr(branch), ptr(acc), n, ns, c, m, p, float(weight), int(_branch), ptr(wsb), nb, stream_ptr(dev))),
+        "remd_loss")
+    return acc[0], rmean, cmean, branch, (u, v, rmin, ridx, cmin, cidx)
+
+
+def remd_loss_backward(x: torch.Tensor, y: torch.Tensor, state, branch: torch.Tensor, grad: torch.Tensor,
+                       weight: float = 1.0) -> torch.Tensor:
+    """d loss / d x [N, C, H, W] of remd_loss from its state and branch, scaled by the device scalar
+    `grad`; nothing flows to y. One launch builds the column branch's inverse lists, one gather launch
+    per branch follows."""
+    x, y, n, ns, c, m, p = _remd_pair(x, y, "remd_loss_backward")
+    u, v, rmin, ridx, cmin, cidx = state
+    dev = x.device
+    want = ((u, n * m, torch.float32), (v, ns * p, torch.float32), (rmin, n * m, torch.float32),
+            (ridx, n * m, torch.int32), (cmin, n * p, torch.float32), (cidx, n * p, torch.int32),
+            (branch, n, torch.uint8), (grad, 1, torch.float32))
+    for t, numel, dt in want:
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or t.numel() != numel:
+            raise HipOpError("remd_loss_backward needs the state and branch of remd_loss on x's shapes and a "
+                             "float32 device scalar grad")
+    u, v, rmin, ridx, cmin, cidx, branch, grad = (t.contiguous() for t, _, _ in want)
+    L = lib()
+    nb = int(L.ast_remd_loss_backward_workspace_bytes(n, m, p))
+    wsb = _ws_bytes(nb, "remd_loss_backward workspace", dev)
+    dx = torch.empty_like(x)
+    check(_timed(f"remd_loss_backward {c}ch {m} vs {p}", -4 * 3 * x.numel(), dev,
+                 lambda: L.ast_remd_loss_backward_f32(
+                     ptr(x), ptr(y), ptr(u), ptr(v), ptr(rmin), ptr(ridx), ptr(cmin), ptr(cidx), ptr(branch),
+                     ptr(grad), ptr(dx), n, ns, c, m, p, float(weight), ptr(wsb), nb, stream_ptr(dev))),
+          "remd_loss_backward")
+    return dx
 
 
 # Guided style swap (csrc/swap.hip): a class >= SWAP_MAX_CLASSES takes no part in the match

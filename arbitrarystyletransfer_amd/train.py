@@ -19,6 +19,10 @@ train.py:248-283, as the reference adds them to the loss:
   out_of_range = 1e8 * huber(stylised, clip(stylised.detach(), 0, 1))          (:259)
   hist         = 1e-5 * compute_hist_loss(stylised, style)                     (:261)
   loss        += hist + org_img + out_of_range                                 (:283)
+With `remd_lam > 0` (an extension, no reference counterpart) the step adds the relaxed earth mover's
+distance between the stylised and the style features at `remd_taps` (losses.compute_remd_loss):
+  loss        += remd_lam * sum_taps remd(lossnet(stylised)[tap], lossnet(style)[tap])
+a batch-mean term. At the default remd_lam = 0 nothing is launched and the step is the one above.
 
 Data parallel (config 4): one process per GPU, each with its own shard of the global batch
 (`args.batch_size` is the global batch, as the reference's --batch_size is the batch of one step;
@@ -132,9 +136,21 @@ _LOSS_IDX = [0, 1, 2, 3, 5, 6]
 _RELU9 = 4
 
 
+# The taps of the relaxed-EMD term (losses.compute_remd_loss): relu4_1 and relu5_1, the 64^2 and 32^2 maps
+# at 512^2 images. Any of _TAPS is legal; a tap costs pixels^2 * channels.
+REMD_TAPS = ("relu_9", "relu_15")
+
+
+def _tap_index(name):
+    if name not in _TAPS:
+        raise ValueError(f"remd_taps: {name!r} is not a tap of the loss network {_TAPS}")
+    return _TAPS.index(name)
+
+
 def default_args(**kw):
     a = dict(train_iter=10, batch_size=8, lr=2e-4, content_lam=1.25, style_lam=0.5, tv_lam=0.0006, lf_lam=1.0,
-             org_img_lam=0.5, save_dir="models/ast/", load=False, image_size=512, full_losses=False)
+             org_img_lam=0.5, save_dir="models/ast/", load=False, image_size=512, full_losses=False,
+             remd_lam=0.0, remd_taps=REMD_TAPS)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -201,6 +217,13 @@ class AdaINTrainer:
         loss = mean_terms + a.tv_lam * tv
         out = {"loss": loss, "content_loss": content_loss, "style_loss": style_loss, "lf_loss": lf_loss,
                "tv_loss": tv, "stylized": stylized, "t": t}
+        remd_lam = float(getattr(a, "remd_lam", 0.0))
+        if remd_lam > 0:   # the relaxed-EMD feature matching term; nothing is launched without it
+            remd_idx = [_tap_index(k) for k in getattr(a, "remd_taps", REMD_TAPS)]
+            remd_loss = torch.stack([L.compute_remd_loss(s_taps[i], taps[i][b:]) for i in remd_idx]).sum()
+            mean_terms = mean_terms + remd_lam * remd_loss
+            loss = loss + remd_lam * remd_loss
+            out.update(loss=loss, remd_loss=remd_loss)
         if getattr(a, "full_losses", False):
             org_out = self.net.decoder(f_c)
             o_taps = self.lossnet(org_out)

@@ -493,6 +493,81 @@ int ast_style_swap_guided_f32(const float* content_key, const float* style_keys,
                               float* score_or_null, int n, int s, int c, int hc, int wc, int hs, int ws,
                               double alpha, void* workspace, long long workspace_bytes, void* stream);
 
+/* Relaxed earth mover's distance style loss (Kolkin et al., STROTSS, CVPR 2019; csrc/remd.hip; an
+ * extension, no reference counterpart): a two-way nearest-neighbour match in cosine distance between
+ * the pixels of two feature maps, exact (every pixel takes part, nothing is sampled), with a backward
+ * to the first map.
+ * Inputs, fp32 dense NCHW with the spatial sides flattened: x [n, c, m], the differentiable side, and
+ * y [ns, c, p] with ns == n, or ns == 1 (one style shared by the batch). Pixel i of x and pixel j of y
+ * are c-vectors. Limits: c in 1..AST_REMD_MAX_C, m and p in 1..AST_REMD_MAX_PIXELS, n <= 65535.
+ * Inverse norms: u_i = 1 / ||x_i||_2, v_j = 1 / ||y_j||_2, exactly 0 when the squared norm is not
+ * positive (or not finite). The squared norm is summed in one fixed order at every position, so equal
+ * vectors have equal inverse norms in bits.
+ * Distance: D(i, j) = 1 - (<x_i, y_j> u_i) v_j, the inner product one fp32 fma chain over the channels
+ * in a fixed order: it depends on the two vectors only, not on where they sit, which tile they fall
+ * in or how the style pixels were split across workgroups. A zero vector is at distance 1 from
+ * everything.
+ * Two-way match: r_i = min_j D(i, j) with arg-min a_i, c_j = min_i D(i, j) with arg-min b_j; the lowest
+ * index on equal values; a NaN never wins; a value replaces the running (+inf, 0) only when strictly
+ * less, so (+inf, 0) is what a pixel without a winner returns. row_min, row_index [n, m] and col_min,
+ * col_index [n, p] (per sample also when ns == 1); the indices are int32. The distances are never stored.
+ * Loss: rbar_b = (sum_i r_i) / m and cbar_b = (sum_j c_j) / p, each summed in a fixed order; sample b
+ * takes the row branch (branch[b] = 1) when rbar_b >= cbar_b and the column branch (branch[b] = 2)
+ * otherwise, and *loss += weight / n * sum_b (row branch ? rbar_b : cbar_b), the samples in a fixed
+ * order: weight * mean_b max(rbar_b, cbar_b). force_branch 1 or 2 gives every sample that branch (a
+ * test hook; 0 is the rule above). loss is a loss accumulator (AST_LOSS_ACC_FLOATS floats, above).
+ * Backward, to x only (y is data). With g = *grad_scale (a device scalar), xh_i = u_i x_i:
+ *   row branch     dx_i = -(g weight / (n m)) u_i (v_a y_a - (1 - r_i) xh_i),   a = a_i
+ *   column branch  dx_i = -(g weight / (n p)) u_i sum over { j : b_j = i }, ascending, of
+ *                         (v_j y_j - (1 - c_j) xh_i)
+ * and exactly 0 where u_i = 0 or, in the column branch, where no column chose i. The lists of the
+ * column branch are built with integer work alone (count, scan, stable fill), no atomics. An index
+ * outside its map given to the backward is clamped into it.
+ * Stages and their composition: ast_remd_loss_f32 is ast_cosine_norms_f32 on x, on y,
+ * ast_cosine_match_f32 with splits 0 and ast_remd_means_f32, bit for bit. Workspaces are device
+ * memory, 256-byte aligned, of at least the matching *_workspace_bytes query. No floating-point
+ * atomics, no host synchronisation, no allocation; a non-finite value stays inside its own sample.
+ * AST_E_NULLPTR: a null pointer. AST_E_SHAPE: a size <= 0 or over the limits above, ns outside {1, n},
+ * a short workspace. AST_E_UNSUPPORTED: c > AST_REMD_MAX_C, splits < 0, force_branch outside 0..2. The
+ * queries return the same negative codes. All checks run before the first launch. */
+#define AST_REMD_MAX_C 1024
+#define AST_REMD_MAX_PIXELS 4194304
+
+/* inv_norm [n, pixels] of x [n, c, pixels]; one launch. */
+int ast_cosine_norms_f32(const float* x, float* inv_norm, int n, int c, int pixels, void* stream);
+
+/* The two-way match from the maps and their inverse norms. The style pixels are split across
+ * workgroups when the content tiles alone cannot fill the chip: splits 0 = the library's choice, else
+ * that many (clamped to the number of 64-pixel style tiles and to 64). The result does not depend on
+ * it, bit for bit. The workspace holds one partial (min, index) pair per 64-pixel content tile and
+ * style pixel, and per split and content pixel: 8 n (ceil(m / 64) p + splits m) bytes and alignment. */
+long long ast_cosine_match_workspace_bytes(int n, int ns, int m, int p, int splits);
+int ast_cosine_match_f32(const float* x, const float* y, const float* inv_x, const float* inv_y,
+                         float* row_min, int* row_index, float* col_min, int* col_index, int n, int ns,
+                         int c, int m, int p, int splits, void* workspace, long long workspace_bytes,
+                         void* stream);
+
+/* row_mean, col_mean [n], branch [n] uint8 and the loss from the minima; two launches. */
+int ast_remd_means_f32(const float* row_min, const float* col_min, float* row_mean, float* col_mean,
+                       unsigned char* branch, float* loss, int n, int m, int p, float weight,
+                       int force_branch, void* stream);
+
+/* The whole forward; every output is also what the backward reads. */
+long long ast_remd_loss_workspace_bytes(int n, int ns, int m, int p);
+int ast_remd_loss_f32(const float* x, const float* y, float* inv_x, float* inv_y, float* row_min,
+                      int* row_index, float* col_min, int* col_index, float* row_mean, float* col_mean,
+                      unsigned char* branch, float* loss, int n, int ns, int c, int m, int p, float weight,
+                      int force_branch, void* workspace, long long workspace_bytes, void* stream);
+
+/* dx [n, c, m] from the forward's outputs: the inverse lists (one launch), then one gather launch per
+ * branch; every element of dx is written. Workspace: 4 n (2 m + 1 + p) bytes and alignment. */
+long long ast_remd_loss_backward_workspace_bytes(int n, int m, int p);
+int ast_remd_loss_backward_f32(const float* x, const float* y, const float* inv_x, const float* inv_y,
+                               const float* row_min, const int* row_index, const float* col_min,
+                               const int* col_index, const unsigned char* branch, const float* grad_scale,
+                               float* dx, int n, int ns, int c, int m, int p, float weight, void* workspace,
+                               long long workspace_bytes, void* stream);
+
 /* Feature k-means and the label mode filter (csrc/kmeans.hip; an extension, no reference counterpart):
  * the stage that makes the uint8 label maps of the regional transforms above from the features
  * themselves, as Multimodal Style Transfer (Zhang et al., ICCV 2019) clusters the style's relu4_1

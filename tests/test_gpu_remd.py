@@ -1,0 +1,340 @@
+"""GPU: the relaxed-EMD style loss (csrc/remd.hip: inverse norms, two-way cosine match, means and
+branch, gather backward) and its wrapper / autograd / registered-op / trainer surface, against
+tests/remd_ref.py.
+
+Bars (remd_ref.py derives them; none comes from the code under test): a returned minimum is within
+OP_TOL = 2e-5 of the float64 distance at the returned index, that distance within 2 * OP_TOL of the float64
+minimum; loss and means within OP_TOL of float64; the branch equal to the reference's; the gradient
+within OP_TOL rel_inf of the float64 analytic gradient evaluated at the GPU's own indices and branch.
+Everything else is bit-for-bit.
+"""
+import functools
+import gc
+
+import pytest
+import torch
+
+import remd_ref as R
+from arbitrarystyletransfer_amd import _lib, functional, library, losses, ops, synth  # noqa: F401  (registers the ops)
+
+pytestmark = pytest.mark.gpu
+
+OP_TOL = R.OP_TOL
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    return R.case_inputs(name)
+
+
+@functools.lru_cache(maxsize=None)
+def _d64(name):
+    return R.distances(*_case(name))
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _mismatches(got, ref):
+    return int((_bits(got) != _bits(ref)).sum())
+
+
+def _flat(t):
+    return t.cpu().reshape(t.shape[0], -1)
+
+
+def _one(dev, v=1.0):
+    return torch.tensor(v, device=dev)
+
+
+# ---- match ------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_cosine_match_against_float64(name, hip_device):
+    x, y = _case(name)
+    n, _, h, w = x.shape
+    hs, ws = y.shape[2:]
+    rmin, ridx, cmin, cidx = ops.cosine_match(x.to(hip_device), y.to(hip_device))
+    assert ridx.dtype == cidx.dtype == torch.int32
+    assert tuple(rmin.shape) == tuple(ridx.shape) == (n, h, w) and tuple(cmin.shape) == tuple(cidx.shape) == (n, hs, ws)
+    assert 0 <= int(ridx.min()) and int(ridx.max()) < hs * ws and 0 <= int(cidx.min()) and int(cidx.max()) < h * w
+    d = _d64(name)
+    e_r, s_r = R.check_axis(_flat(rmin), _flat(ridx), d)
+    e_c, s_c = R.check_axis(_flat(cmin), _flat(cidx), d.transpose(1, 2))
+    print(f"cosine_match {name}: value error rows {e_r:.2e}, columns {e_c:.2e} (bar {OP_TOL:.0e}); index shortfall "
+          f"rows {s_r:.2e}, columns {s_c:.2e} (bar {2 * OP_TOL:.0e})")
+    assert max(e_r, e_c) <= OP_TOL and max(s_r, s_c) <= 2 * OP_TOL
+
+
+@pytest.mark.parametrize("name", ["c512_split_keys", "c160_tile_tails"])
+def test_split_counts_agree_bitwise(name, hip_device):
+    x, y = (t.to(hip_device) for t in _case(name))
+    one, four, auto = (ops.cosine_match(x, y, _splits=k) for k in (1, 4, 0))
+    bad = [_mismatches(a, b) for other in (four, auto) for a, b in zip(one, other)]
+    print(f"{name}: 1 split vs 4 vs the library's choice: {bad} mismatches")
+    assert bad == [0] * 8
+
+
+def test_planted_vector_is_found(hip_device):
+    x, y = (t.clone() for t in _case("c64_shared_style"))
+    x[1, :, 7, 5] = 3.0 * y[0, :, 9, 11]              # a scaled copy: cosine distance 0
+    rmin, ridx, cmin, cidx = ops.cosine_match(x.to(hip_device), y.to(hip_device))
+    i, j = 7 * 13 + 5, 9 * 15 + 11
+    print(f"planted: row ({float(rmin[1, 7, 5]):.2e}, {int(ridx[1, 7, 5])}), column ({float(cmin[1, 9, 11]):.2e}, "
+          f"{int(cidx[1, 9, 11])}); want indices {j}, {i}")
+    assert int(ridx[1, 7, 5]) == j and int(cidx[1, 9, 11]) == i
+    assert abs(float(rmin[1, 7, 5])) <= OP_TOL and abs(float(cmin[1, 9, 11])) <= OP_TOL
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+def test_exact_ties_take_the_lowest_index_on_both_axes(splits, hip_device):
+    """Style pixels j and j + 100 are equal bit for bit and sit in different 64-pixel tiles (and splits);
+    content pixels i and i + 90 likewise, in different workgroups: the lower one wins every time."""
+    by, bx = R.features(11910, (1, 16, 1, 100)), R.features(11911, (1, 16, 1, 90))
+    y, x = torch.cat([by, by], dim=3), torch.cat([bx, bx], dim=3)
+    rmin, ridx, cmin, cidx = ops.cosine_match(x.to(hip_device), y.to(hip_device), _splits=splits)
+    hi_r, hi_c = int((ridx >= 100).sum()), int((cidx >= 90).sum())
+    print(f"duplicates, {splits} split(s): {hi_r} row and {hi_c} column indices are the higher duplicate")
+    assert hi_r == 0 and hi_c == 0
+    assert _mismatches(rmin[..., :90], rmin[..., 90:]) == 0 and _mismatches(cmin[..., :100], cmin[..., 100:]) == 0
+
+
+def test_zero_vectors(hip_device):
+    x = R.features(11912, (1, 8, 9, 10)) + 0.01
+    y = R.features(11913, (1, 8, 7, 11)) + 0.01
+    x[:, :, 2, 3] = 0.0            # content pixel 23
+    y[:, :, 6, 4] = 0.0            # style pixel 70, in the second tile
+    xd, yd = x.to(hip_device), y.to(hip_device)
+    assert float(ops.cosine_norms(xd)[0, 2, 3]) == 0.0 and float(ops.cosine_norms(yd)[0, 6, 4]) == 0.0
+    rmin, ridx, cmin, cidx = ops.cosine_match(xd, yd)
+    print(f"zero vectors: row ({float(rmin[0, 2, 3])}, {int(ridx[0, 2, 3])}), column ({float(cmin[0, 6, 4])}, "
+          f"{int(cidx[0, 6, 4])})")
+    assert float(rmin[0, 2, 3]) == 1.0 and int(ridx[0, 2, 3]) == 0          # distance 1 to everything: the first
+    assert float(cmin[0, 6, 4]) == 1.0 and int(cidx[0, 6, 4]) == 0
+    assert int((ridx == 70).sum()) == 0 and int((cidx == 23).sum()) == 0      # and nobody else picks them
+    for branch in (R.ROW, R.COL):
+        loss, _, _, br, state = ops.remd_loss(xd, yd, 1.0, _branch=branch)
+        dx = ops.remd_loss_backward(xd, yd, state, br, _one(hip_device), 1.0)
+        assert bool(torch.isfinite(dx).all()) and float(dx[0, :, 2, 3].abs().max()) == 0.0
+
+
+def test_nan_stays_inside_its_sample(hip_device):
+    x, y = (t.to(hip_device) for t in _case("c48_k_tails"))
+    xn, yn = x.clone(), y.clone()
+    xn[1, 5, 3, 4] = float("nan")
+    yn[1, 7, 2, 2] = float("inf")
+    bad = []
+    for branch in (R.ROW, R.COL):
+        a = ops.remd_loss(x, y, 1.0, _branch=branch)
+        b = ops.remd_loss(xn, yn, 1.0, _branch=branch)
+        da = ops.remd_loss_backward(x, y, a[4], a[3], _one(hip_device), 1.0)
+        db = ops.remd_loss_backward(xn, yn, b[4], b[3], _one(hip_device), 1.0)
+        bad += [_mismatches(s[0], t[0]) for s, t in zip(a[4][2:], b[4][2:])] + [_mismatches(da[0], db[0])]
+        bad += [_mismatches(a[1][0], b[1][0]), _mismatches(a[2][0], b[2][0])]
+    print(f"NaN / inf in sample 1: mismatches in sample 0 (minima, indices, gradient, means per branch): {bad}")
+    assert not any(bad)
+    rmin, ridx, _, _ = ops.cosine_match(xn, yn)
+    assert int(ridx[1].min()) >= 0 and int(ridx[1].max()) < y.shape[2] * y.shape[3]   # a NaN never wins
+
+
+# ---- loss and backward ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_remd_loss_forward_against_float64(name, hip_device):
+    x, y = _case(name)
+    loss, rm, cm, br, _ = ops.remd_loss(x.to(hip_device), y.to(hip_device), 1.0)
+    l64, rm64, cm64, br64 = R.loss(x, y)
+    e = [abs(float(loss) - float(l64)), float((rm.cpu().double() - rm64).abs().max()),
+         float((cm.cpu().double() - cm64).abs().max())]
+    print(f"remd_loss {name}: loss {float(loss):.6f} (float64 {float(l64):.6f}); errors loss {e[0]:.2e}, row mean "
+          f"{e[1]:.2e}, column mean {e[2]:.2e} (bar {OP_TOL:.0e}); branch {br.tolist()} (float64 {br64.tolist()})")
+    assert br.dtype == torch.uint8 and br.tolist() == br64.tolist() and max(e) <= OP_TOL
+    if name == "c8_one_pixel":
+        assert br.tolist() == [R.ROW] and _mismatches(rm, cm) == 0          # equal means: the row branch
+    half = ops.remd_loss(x.to(hip_device), y.to(hip_device), 0.5)[0]
+    assert abs(float(half) - 0.5 * float(l64)) <= OP_TOL
+
+
+@pytest.mark.parametrize("branch", [0, R.ROW, R.COL])
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_remd_loss_backward_against_float64(name, branch, hip_device):
+    x, y = _case(name)
+    xd, yd = x.to(hip_device), y.to(hip_device)
+    weight, g = 0.8, 1.5
+    _, _, _, br, state = ops.remd_loss(xd, yd, weight, _branch=branch)
+    dx = ops.remd_loss_backward(xd, yd, state, br, _one(hip_device, g), weight).cpu()
+    index = (state[3].cpu(), state[5].cpu())
+    if branch:
+        assert br.tolist() == [branch] * x.shape[0]
+    ref = R.grad(x, y, weight, g, index=index, branch=br.cpu())
+    emu = R.grad(x, y, weight, g, dtype=torch.float32, index=index, branch=br.cpu())
+    err, e_emu = R.rel_inf(dx, ref), R.rel_inf(emu, ref)
+    print(f"remd_loss_backward {name} _branch={branch} (took {br.tolist()}): rel_inf {err:.2e} (bar {OP_TOL:.0e}; the "
+          f"fp32 emulation: {e_emu:.2e}); max |grad| {float(ref.abs().max()):.2e}")
+    assert tuple(dx.shape) == tuple(x.shape) and err <= OP_TOL
+
+
+def test_autograd_equals_the_backward_kernels_bitwise(hip_device):
+    x, y = (t.to(hip_device) for t in _case("c64_shared_style"))
+    xg, yg = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
+    loss = losses.compute_remd_loss(xg, yg, 0.7)
+    (dx,) = torch.autograd.grad(2.0 * loss, xg)
+    want_loss, _, _, br, state = ops.remd_loss(x, y, 0.7)
+    want = ops.remd_loss_backward(x, y, state, br, _one(hip_device, 2.0), 0.7)
+    fn = functional.RemdLossFn.apply(xg, yg, 0.7)
+    (dfn,) = torch.autograd.grad(2.0 * fn, xg)
+    bad = [_mismatches(loss.reshape(1), want_loss.reshape(1)), _mismatches(dx, want), _mismatches(fn.reshape(1),
+           want_loss.reshape(1)), _mismatches(dfn, want)]
+    print(f"compute_remd_loss / RemdLossFn vs ops: {bad} mismatches (loss, gradient, loss, gradient)")
+    assert bad == [0, 0, 0, 0]
+
+
+def test_style_gets_no_gradient(hip_device):
+    x, y = (t.to(hip_device).requires_grad_(True) for t in _case("c48_k_tails"))
+    loss = losses.compute_remd_loss(x, y)
+    dx, dy = torch.autograd.grad(loss, (x, y), allow_unused=True)
+    assert dy is None and dx is not None and float(dx.abs().max()) > 0
+    small = R.features(11914, (2, 48, 3, 4)).to(hip_device)                  # a style map of another size, a batch of 1
+    assert bool(torch.isfinite(losses.compute_remd_loss(x, small[:1])))
+
+
+def test_stages_compose_to_the_whole_op_bitwise(hip_device):
+    for name in ("c48_k_tails", "c512_split_keys"):
+        x, y = (t.to(hip_device) for t in _case(name))
+        loss, rm, cm, br, state = ops.remd_loss(x, y, 0.9)
+        u, v = ops.cosine_norms(x), ops.cosine_norms(y)
+        m = ops.cosine_match(x, y)
+        sl, srm, scm, sbr = ops.remd_means(m[0], m[2], 0.9)
+        bad = [_mismatches(a, b) for a, b in zip((u, v) + tuple(m) + (sl.reshape(1), srm, scm, sbr),
+                                                 tuple(state) + (loss.reshape(1), rm, cm, br))]
+        print(f"{name}: stages vs the whole op: {bad} mismatches")
+        assert not any(bad)
+
+
+def _everything(x, y, one, branch=0):
+    loss, rm, cm, br, state = ops.remd_loss(x, y, 1.0, _branch=branch)
+    dx = ops.remd_loss_backward(x, y, state, br, one, 1.0)
+    return (loss.reshape(1), rm, cm, br, dx) + tuple(state)
+
+
+def test_run_twice_bitwise(hip_device):
+    for name in ("c64_shared_style", "c32_many_queries", "c24_few_content"):
+        x, y = (t.to(hip_device) for t in _case(name))
+        for branch in (R.ROW, R.COL):
+            a, b = (_everything(x, y, _one(hip_device), branch) for _ in range(2))
+            bad = [_mismatches(s, t) for s, t in zip(a, b)]
+            assert not any(bad), (name, branch, bad)
+
+
+def test_graph_replay_equals_eager(hip_device):
+    x, y = (t.to(hip_device) for t in _case("c64_shared_style"))
+    one = _one(hip_device)
+    eager = [_everything(x, y, one, br) for br in (R.ROW, R.COL)]
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g):
+            out = [_everything(x, y, one, br) for br in (R.ROW, R.COL)]
+    finally:
+        gc.enable()
+    for t in (t for o in out for t in o):
+        t.fill_(0) if t.dtype != torch.float32 else t.fill_(float("nan"))
+    g.replay()
+    g.replay()   # the accumulator's zero fill is captured too: a second replay gives the same loss
+    torch.cuda.synchronize()
+    bad = [_mismatches(s, t) for a, b in zip(eager, out) for s, t in zip(a, b)]
+    print(f"graph replay vs eager: {bad} mismatches")
+    assert not any(bad)
+
+
+def test_registered_op_equals_ctypes_path_bitwise(hip_device):
+    x, y = (t.to(hip_device) for t in _case("c160_tile_tails"))
+    out = torch.ops.ast_hip.remd_loss(x, y, 0.6, 0)
+    loss, rm, cm, br, state = ops.remd_loss(x, y, 0.6)
+    bad = [_mismatches(a, b) for a, b in zip(out, (loss.reshape(1), rm, cm, br) + tuple(state))]
+    assert not any(bad), bad
+    m = torch.device("meta")
+    fake = torch.ops.ast_hip.remd_loss(x.to(m), y.to(m), 0.6, 0)
+    assert [(tuple(t.shape), t.dtype) for t in fake] == [(tuple(t.shape), t.dtype) for t in out]
+
+
+def test_wrappers_reject_bad_inputs(hip_device):
+    d = hip_device
+    f = lambda *s: torch.zeros(*s, device=d)  # noqa: E731
+    bad = [
+        lambda: ops.cosine_match(torch.zeros(1, 8, 2, 2), f(1, 8, 2, 2)),             # a CPU tensor
+        lambda: ops.remd_loss(f(1, 8, 2, 2), torch.zeros(1, 8, 2, 2)),
+        lambda: ops.cosine_match(f(1, 8, 2, 2), f(1, 9, 2, 2)),                        # C mismatch
+        lambda: ops.remd_loss(f(3, 8, 2, 2), f(2, 8, 2, 2)),                           # a style batch neither N nor 1
+        lambda: ops.cosine_match(f(1, 8, 0, 2), f(1, 8, 2, 2)),                        # empty maps
+        lambda: ops.remd_loss(f(1, 8, 2, 2), f(1, 8, 2, 0)),
+        lambda: ops.cosine_match(f(8, 2, 2), f(1, 8, 2, 2)),                           # not 4-D
+        lambda: ops.cosine_match(f(1, 8, 2, 2).double(), f(1, 8, 2, 2)),               # not float32
+        lambda: ops.remd_loss(f(1, ops.REMD_MAX_C + 1, 1, 1), f(1, ops.REMD_MAX_C + 1, 1, 1)),   # past the limits
+        lambda: ops.cosine_match(f(1, 1, 1, 1), f(1, 1, 2049, 2049)),
+        lambda: ops.remd_loss(f(1, 8, 2, 2), f(1, 8, 2, 2), _branch=3),
+        lambda: losses.compute_remd_loss(f(1, 8, 2, 2), f(1, 9, 2, 2)),
+    ]
+    for call in bad:
+        with pytest.raises(_lib.HipOpError):
+            call()
+    L = _lib.lib()
+    assert L.ast_cosine_norms_f32(1, 1, 1, ops.REMD_MAX_C + 1, 4, None) == -3          # and the C ABI itself
+    assert L.ast_cosine_norms_f32(1, 1, 1, 8, ops.REMD_MAX_PIXELS + 1, None) == -2
+    x, y = f(1, 8, 2, 2) + 1, f(1, 8, 2, 2) + 1
+    _, _, _, br, state = ops.remd_loss(x, y)
+    with pytest.raises(_lib.HipOpError):
+        ops.remd_loss_backward(x, y, state, br, torch.tensor(1.0), 1.0)                # the scalar on the CPU
+    with pytest.raises(_lib.HipOpError):
+        ops.remd_loss_backward(x, y, state[:5] + (state[5].long(),), br, _one(d), 1.0)
+
+
+# ---- trainer ------------------------------------------------------------------------------------------
+
+def _trainer(dev, **kw):
+    from arbitrarystyletransfer_amd.train import AdaINTrainer, default_args
+    torch.manual_seed(1234)
+    return AdaINTrainer(default_args(batch_size=2, image_size=64, **kw), device=dev)
+
+
+def test_trainer_term(hip_device):
+    from arbitrarystyletransfer_amd import train
+    assert train.default_args().remd_lam == 0.0
+    c = torch.from_numpy(synth.image(4321, (2, 3, 64, 64))).to(hip_device)
+    s = torch.from_numpy(synth.image(4322, (2, 3, 64, 64))).to(hip_device)
+    base, tr = _trainer(hip_device), _trainer(hip_device, remd_lam=1.0)
+    tr.net.load_state_dict(base.net.state_dict())
+    out0 = base.compute_losses(c, s)
+    assert "remd_loss" not in out0
+    out0["loss"].backward()
+    g0 = [p.grad.clone() for p in base.params]
+    out1 = tr.compute_losses(c, s)
+    with torch.no_grad():
+        taps, s_taps = tr.lossnet(c, s), tr.lossnet(out1["stylized"])
+        want = sum(losses.compute_remd_loss(s_taps[i], taps[i][2:]) for i in (train._tap_index(k) for k in tr.args.remd_taps))
+    assert _mismatches(out1["remd_loss"].reshape(1), want.reshape(1)) == 0 and float(want) > 0
+    total = float(out0["loss"].detach()) + 1.0 * float(out1["remd_loss"].detach())
+    got = float(out1["loss"].detach())
+    print(f"trainer: remd_loss {float(want):.6f}; loss {got:.6f} vs base + term {total:.6f}")
+    assert abs(got - total) <= 1e-6 * abs(total)
+    assert set(out1) - set(out0) == {"remd_loss"}
+    out1["loss"].backward()
+    g1 = [p.grad.clone() for p in tr.params]
+    assert all(bool(torch.isfinite(g).all()) for g in g1)
+    assert any(_mismatches(a, b) for a, b in zip(g0, g1))
+
+
+def test_trainer_step_is_deterministic(hip_device):
+    c = torch.from_numpy(synth.image(4321, (2, 3, 64, 64))).to(hip_device)
+    s = torch.from_numpy(synth.image(4322, (2, 3, 64, 64))).to(hip_device)
+    a, b = _trainer(hip_device, remd_lam=1.0), _trainer(hip_device, remd_lam=1.0)
+    b.net.load_state_dict(a.net.state_dict())
+    keys = list(a.train_dict)
+    oa, ob = a.train_step(c, s, record=True), b.train_step(c, s, record=True)
+    assert list(a.train_dict) == keys == ["content_loss", "style_loss", "lf_loss", "tv_loss", "org_img_loss"]
+    bad = [_mismatches(oa[k].reshape(-1), ob[k].reshape(-1)) for k in ("loss", "remd_loss", "grad_norm")]
+    bad += [_mismatches(p, q) for p, q in zip(a.params, b.params)]
+    assert not any(bad), bad
