@@ -89,6 +89,15 @@ SIGNATURES = {
     "ast_remd_loss_f32": (_i, [_p] * 12 + [_i] * 5 + [_f, _i, _p, _ll, _p]),
     "ast_remd_loss_backward_workspace_bytes": (_ll, [_i, _i, _i]),
     "ast_remd_loss_backward_f32": (_i, [_p] * 11 + [_i] * 5 + [_f, _p, _ll, _p]),
+    "ast_selfsim_colsum_workspace_bytes": (_ll, [_i, _i]),
+    "ast_selfsim_colsum_f32": (_i, [_p, _p, _p, _i, _i, _i, _p, _ll, _p]),
+    "ast_selfsim_pairs_workspace_bytes": (_ll, [_i, _i]),
+    "ast_selfsim_pairs_f32": (_i, [_p] * 10 + [_i, _i, _i, _p, _ll, _p]),
+    "ast_selfsim_total_f32": (_i, [_p, _p, _i, _f, _p]),
+    "ast_selfsim_loss_workspace_bytes": (_ll, [_i, _i, _i]),
+    "ast_selfsim_loss_f32": (_i, [_p] * 11 + [_i, _i, _i, _f, _p, _ll, _p]),
+    "ast_selfsim_loss_backward_workspace_bytes": (_ll, [_i, _i, _i]),
+    "ast_selfsim_loss_backward_f32": (_i, [_p] * 8 + [_i, _i, _i, _f, _p, _ll, _p]),
     "ast_kmeans_workspace_bytes":(_ll, [_i, _i, _i, _i, _i]),
     "ast_kmeans_seed_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "ast_kmeans_assign_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

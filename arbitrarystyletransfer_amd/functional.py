@@ -716,6 +716,24 @@ class RemdLossFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+class SelfSimLossFn(torch.autograd.Function):
+    """weight * the self-similarity content loss between the pixel-pair distances inside x and inside c
+    (ops.selfsim_loss); c is data (no gradient) and is not saved."""
+
+    @staticmethod
+    def forward(ctx, x, c, weight):
+        x, c = _dev(x, "t_cs_map"), _dev(c, "content_map")
+        loss, _, state = ops.selfsim_loss(x, c, float(weight), acc=_acc(x))
+        ctx.save_for_backward(x, *state)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, *state = ctx.saved_tensors
+        return ops.selfsim_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None
+
+
 class RangeLossFn(torch.autograd.Function):
     """weight * compute_content_loss(x, torch.clip(x.detach(), 0, 1)) (train.py:259)."""
 

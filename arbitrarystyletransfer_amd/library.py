@@ -22,6 +22,7 @@ huber_loss              losses.py:124-126 (compute_content_loss)     d x, d y
 tv_loss                 losses.py:90-103                             d img
 hist_loss               losses.py:84-87 (SingleDimHist + EMD)        d x
 remd_loss               -- (relaxed EMD: two-way cosine match)       d x
+selfsim_loss            -- (self-similarity of pixel-pair distances) d x
 range_loss              train.py:259                                 d x
 sqdiff_mean             train.py:268                                 d x
 mb_expand_dw            mobilenetv2.py:153-161 (to the SE pool)      -- (eval BN folded: inference)
@@ -472,6 +473,36 @@ def _remd_backward(ctx, g, *_):
 register_autograd("ast_hip::remd_loss", _remd_backward, setup_context=_remd_setup)
 
 
+@custom_op("ast_hip::selfsim_loss", mutates_args=())
+def selfsim_loss(x: Tensor, c: Tensor, weight: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor,
+                                                               Tensor, Tensor]:
+    """weight * the self-similarity content loss of ops.selfsim_loss; outputs (loss, per_sample, inv_x, inv_c,
+    r_x, r_c, t, pos, neg)."""
+    loss, sums, state = ops.selfsim_loss(x, c, float(weight), acc=_acc(x))
+    return (loss, sums) + tuple(state)
+
+
+@register_fake("ast_hip::selfsim_loss")
+def _(x, c, weight):
+    n, (h, w) = x.shape[0], x.shape[2:]
+    planes = (n, h * w, (h * w + 63) // 64)
+    return ((x.new_empty(()), x.new_empty((n,))) + tuple(x.new_empty((n, h, w)) for _ in range(5))
+            + (x.new_empty(planes, dtype=torch.int64), x.new_empty(planes, dtype=torch.int64)))
+
+
+def _selfsim_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], *output[2:])
+    ctx.weight = float(inputs[2])
+
+
+def _selfsim_backward(ctx, g, *_):
+    x, *state = ctx.saved_tensors
+    return ops.selfsim_loss_backward(x, tuple(state), g.contiguous(), ctx.weight), None, None
+
+
+register_autograd("ast_hip::selfsim_loss", _selfsim_backward, setup_context=_selfsim_setup)
+
+
 @custom_op("ast_hip::range_loss", mutates_args=())
 def range_loss(x: Tensor, weight: float) -> Tensor:
     acc = _acc(x)
@@ -917,7 +948,8 @@ def _(labels, regions, passes):
 
 
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
-                  "remd_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw", "mb_expand_gemm",
-                  "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer", "resize_labels",
+                  "remd_loss", "selfsim_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw",
+                  "mb_expand_gemm", "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer",
+                  "resize_labels",
                   "region_stats", "adain_regions", "efdm", "plane_sort", "efdm_regions", "wct", "wct_regions",
                   "style_swap", "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]

@@ -62,7 +62,7 @@ __all__ = ["gram_matrix", "compute_content_loss", "compute_style_loss", "tv_loss
            "content_mvn_loss", "style_loss_weighted", "content_style_loss", "EarthMoversDistanceLoss",
            "HistLayerBase",
            "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss",
-           "compute_efdm_loss", "compute_remd_loss"]
+           "compute_efdm_loss", "compute_remd_loss", "compute_selfsim_loss"]
 
 
 def gram_matrix(tensor):
@@ -175,6 +175,16 @@ def compute_remd_loss(t_cs_map, style_map, weight: float = 1.0):
     through the HIP gather backward (torch.ops.ast_hip.remd_loss)."""
     x, y = _dev(t_cs_map, "t_cs_map"), _dev(style_map.detach(), "style_map")
     return _ops.remd_loss(x, y, float(weight), 0)[0]
+
+
+def compute_selfsim_loss(t_cs_map, content_map, weight: float = 1.0):
+    """The self-similarity content loss of one loss tap (Kolkin et al., STROTSS, CVPR 2019), exact rather
+    than sampled: with D_f the cosine distances between every two pixels of a map f [N, C, H, W], each
+    column divided by its sum, weight * mean over the batch of (1 / HW) sum_{i != j} |D_x(i, j) / r_x(j) -
+    D_c(i, j) / r_c(j)| for x = t_cs_map and c = content_map (same shape). The content map is detached; the
+    gradient reaches t_cs_map through the HIP backward (torch.ops.ast_hip.selfsim_loss)."""
+    x, c = _dev(t_cs_map, "t_cs_map"), _dev(content_map.detach(), "content_map")
+    return _ops.selfsim_loss(x, c, float(weight))[0]
 
 
 def out_of_range_loss(img, weight: float = 1e8):

@@ -906,6 +906,133 @@ def remd_loss_backward(x: torch.Tensor, y: torch.Tensor, state, branch: torch.Te
     return dx
 
 
+# Self-similarity content loss (csrc/selfsim.hip): AST_SELFSIM_MAX_PIXELS of ast_hip.h, where the two sign
+# planes take 64 MiB per sample
+SELFSIM_MAX_PIXELS = 1 << 14
+
+
+def _selfsim_pair(x: torch.Tensor, c: torch.Tensor, what: str):
+    """Two fp32 device NCHW maps of equal shape inside the limits of csrc/selfsim.hip: (x, c, n, ch, pixels).
+    The checks of _remd_pair, and equal shapes."""
+    x, c, n, _, ch, m, _ = _remd_pair(x, c, what)
+    if x.shape != c.shape:
+        raise HipOpError(f"{what} needs maps of equal shape: x {tuple(x.shape)} vs c {tuple(c.shape)}")
+    if m > SELFSIM_MAX_PIXELS:
+        raise HipOpError(f"{what}: a map has at most {SELFSIM_MAX_PIXELS} pixels, got {tuple(x.shape)}")
+    return x, c, n, ch, m
+
+
+def _selfsim_like(t, x: torch.Tensor, shape, dtype, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise HipOpError(f"{what} must be a {dtype} tensor {tuple(shape)} on {x.device}")
+    return t.contiguous()
+
+
+def _selfsim_planes(x: torch.Tensor):
+    n, _, h, w = x.shape
+    return (n, h * w, (h * w + 63) // 64)
+
+
+def selfsim_colsum(x: torch.Tensor, inv_norm: torch.Tensor) -> torch.Tensor:
+    """r [N, H, W]: r(j) = sum_i D(i, j) over the pixels i != j of the same sample, D the cosine distance
+    between pixels of x [N, C, H, W], from inv_norm = cosine_norms(x); computed as (HW - 1) - (<xh_j, S> -
+    ||xh_j||^2) with S the sum of the unit vectors: no pass over pairs."""
+    x, _, n, ch, m = _selfsim_pair(x, x, "selfsim_colsum")
+    u = _selfsim_like(inv_norm, x, (n,) + tuple(x.shape[2:]), torch.float32, "selfsim_colsum: inv_norm")
+    L, dev = lib(), x.device
+    nb = int(L.ast_selfsim_colsum_workspace_bytes(n, ch))
+    wsb = _ws_bytes(nb, "selfsim_colsum workspace", dev)
+    r = torch.empty_like(u)
+    check(L.ast_selfsim_colsum_f32(ptr(x), ptr(u), ptr(r), n, ch, m, ptr(wsb), nb, stream_ptr(dev)), "selfsim_colsum")
+    return r
+
+
+def selfsim_pairs(x: torch.Tensor, c: torch.Tensor, inv_x: torch.Tensor, inv_c: torch.Tensor, r_x: torch.Tensor,
+                  r_c: torch.Tensor):
+    """The pass over the pixel pairs of the self-similarity loss: (sums [N], t [N, H, W], pos, neg int64
+    [N, HW, ceil(HW / 64)]). With e(i, j) = D_x(i, j) / r_x(j) - D_c(i, j) / r_c(j) (1 / r taken as 0
+    unless r is positive and finite), sums[b] = (1 / HW) sum_{i != j} |e|, t(j) = (1 / r_x(j)) sum_k
+    sign(e(k, j)) D_x(k, j), and bit k of word (i, J) of pos / neg is set where e(i, 64 J + k) > 0 / < 0."""
+    x, c, n, ch, m = _selfsim_pair(x, c, "selfsim_pairs")
+    shp = (n,) + tuple(x.shape[2:])
+    u, v, rx, rc = (_selfsim_like(t, x, shp, torch.float32, f"selfsim_pairs: {k}")
+                    for t, k in ((inv_x, "inv_x"), (inv_c, "inv_c"), (r_x, "r_x"), (r_c, "r_c")))
+    L, dev = lib(), x.device
+    nb = int(L.ast_selfsim_pairs_workspace_bytes(n, m))
+    wsb = _ws_bytes(nb, "selfsim_pairs workspace", dev)
+    sums = torch.empty((n,), device=dev, dtype=torch.float32)
+    t = torch.empty(shp, device=dev, dtype=torch.float32)
+    pos = torch.empty(_selfsim_planes(x), device=dev, dtype=torch.int64)
+    neg = torch.empty_like(pos)
+    check(_timed(f"selfsim_pairs {ch}ch {m}", 2 * n * m * m * ch, dev, lambda: L.ast_selfsim_pairs_f32(
+        ptr(x), ptr(c), ptr(u), ptr(v), ptr(rx), ptr(rc), ptr(sums), ptr(t), ptr(pos), ptr(neg), n, ch, m, ptr(wsb),
+        nb, stream_ptr(dev))), "selfsim_pairs")
+    return sums, t, pos, neg
+
+
+def selfsim_total(sums: torch.Tensor, weight: float = 1.0, acc=None) -> torch.Tensor:
+    """weight * mean of the per-sample values of selfsim_pairs: the last stage of selfsim_loss. `acc`: the
+    loss accumulator the value is added into (a fresh one if None)."""
+    if (not isinstance(sums, torch.Tensor) or sums.device.type != "cuda" or sums.dtype != torch.float32
+            or sums.dim() != 1 or sums.numel() == 0):
+        raise HipOpError("selfsim_total needs the float32 device sums [N] of selfsim_pairs")
+    sums, dev = sums.contiguous(), sums.device
+    acc = loss_accumulator(dev) if acc is None else acc
+    check(lib().ast_selfsim_total_f32(ptr(sums), ptr(acc), int(sums.numel()), float(weight), stream_ptr(dev)),
+          "selfsim_total")
+    return acc[0]
+
+
+def selfsim_loss(x: torch.Tensor, c: torch.Tensor, weight: float = 1.0, acc=None):
+    """The self-similarity content loss (Kolkin et al., CVPR 2019), exact: weight * mean over the batch of
+    (1 / HW) sum_{i != j} |D_x(i, j) / r_x(j) - D_c(i, j) / r_c(j)|, D the cosine distances between the pixels
+    inside x (the stylised map) and inside c (the content map, same shape), r their column sums. Returns
+    (loss, per_sample [N], state); state = (inv_x, inv_c, r_x, r_c, t, pos, neg) is what
+    selfsim_loss_backward reads. The distance matrices are never stored."""
+    x, c, n, ch, m = _selfsim_pair(x, c, "selfsim_loss")
+    L, dev = lib(), x.device
+    nb = int(L.ast_selfsim_loss_workspace_bytes(n, ch, m))
+    wsb = _ws_bytes(nb, "selfsim_loss workspace", dev)
+    shp = (n,) + tuple(x.shape[2:])
+    u, v, rx, rc, t = (torch.empty(shp, device=dev, dtype=torch.float32) for _ in range(5))
+    pos = torch.empty(_selfsim_planes(x), device=dev, dtype=torch.int64)
+    neg = torch.empty_like(pos)
+    sums = torch.empty((n,), device=dev, dtype=torch.float32)
+    acc = loss_accumulator(dev) if acc is None else acc
+    check(_timed(f"selfsim_loss {ch}ch {m}", 2 * n * m * m * ch, dev, lambda: L.ast_selfsim_loss_f32(
+        ptr(x), ptr(c), ptr(u), ptr(v), ptr(rx), ptr(rc), ptr(t), ptr(pos), ptr(neg), ptr(sums), ptr(acc), n, ch, m,
+        float(weight), ptr(wsb), nb, stream_ptr(dev))), "selfsim_loss")
+    return acc[0], sums, (u, v, rx, rc, t, pos, neg)
+
+
+def selfsim_loss_backward(x: torch.Tensor, state, grad: torch.Tensor, weight: float = 1.0) -> torch.Tensor:
+    """d loss / d x [N, C, H, W] of selfsim_loss from its state, scaled by the device scalar `grad`; nothing
+    flows to the content map, which is not read. A GEMM of the weights rebuilt from the sign planes with
+    x, then the normalisation backward; no cosine is recomputed."""
+    x, _, n, ch, m = _selfsim_pair(x, x, "selfsim_loss_backward")
+    if not isinstance(state, (tuple, list)) or len(state) != 7:
+        raise HipOpError("selfsim_loss_backward needs the state (inv_x, inv_c, r_x, r_c, t, pos, neg) of selfsim_loss")
+    shp, pshape = (n,) + tuple(x.shape[2:]), _selfsim_planes(x)
+    what = "selfsim_loss_backward: {}"
+    u = _selfsim_like(state[0], x, shp, torch.float32, what.format("inv_x"))
+    rx = _selfsim_like(state[2], x, shp, torch.float32, what.format("r_x"))
+    t = _selfsim_like(state[4], x, shp, torch.float32, what.format("t"))
+    pos = _selfsim_like(state[5], x, pshape, torch.int64, what.format("pos"))
+    neg = _selfsim_like(state[6], x, pshape, torch.int64, what.format("neg"))
+    if not isinstance(grad, torch.Tensor) or grad.device != x.device or grad.dtype != torch.float32 or grad.numel() != 1:
+        raise HipOpError("selfsim_loss_backward needs a float32 device scalar grad")
+    grad = grad.contiguous()
+    L, dev = lib(), x.device
+    nb = int(L.ast_selfsim_loss_backward_workspace_bytes(n, ch, m))
+    wsb = _ws_bytes(nb, "selfsim_loss_backward workspace", dev)
+    dx = torch.empty_like(x)
+    check(_timed(f"selfsim_loss_backward {ch}ch {m}", 2 * n * m * m * ch, dev,
+                 lambda: L.ast_selfsim_loss_backward_f32(
+                     ptr(x), ptr(u), ptr(rx), ptr(t), ptr(pos), ptr(neg), ptr(grad), ptr(dx), n, ch, m, float(weight),
+                     ptr(wsb), nb, stream_ptr(dev))), "selfsim_loss_backward")
+    return dx
+
+
 # Guided style swap (csrc/swap.hip): a class >= SWAP_MAX_CLASSES takes no part in the match
 SWAP_MAX_CLASSES = 64
 _SWAP_NO_SKIP = 1   # AST_SWAP_NO_SKIP

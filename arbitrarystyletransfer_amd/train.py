@@ -23,6 +23,10 @@ With `remd_lam > 0` (an extension, no reference counterpart) the step adds the r
 distance between the stylised and the style features at `remd_taps` (losses.compute_remd_loss):
   loss        += remd_lam * sum_taps remd(lossnet(stylised)[tap], lossnet(style)[tap])
 a batch-mean term. At the default remd_lam = 0 nothing is launched and the step is the one above.
+With `selfsim_lam > 0` (an extension likewise) it adds the self-similarity content loss of the same paper
+between the stylised and the content features at `selfsim_taps` (losses.compute_selfsim_loss):
+  loss        += selfsim_lam * sum_taps selfsim(lossnet(stylised)[tap], lossnet(content)[tap])
+a batch-mean term too; at the default selfsim_lam = 0 nothing is launched.
 
 Data parallel (config 4): one process per GPU, each with its own shard of the global batch
 (`args.batch_size` is the global batch, as the reference's --batch_size is the batch of one step;
@@ -141,16 +145,21 @@ _RELU9 = 4
 REMD_TAPS = ("relu_9", "relu_15")
 
 
-def _tap_index(name):
+# The taps of the self-similarity term (losses.compute_selfsim_loss): the same two; a tap's map may have at
+# most ops.SELFSIM_MAX_PIXELS pixels.
+SELFSIM_TAPS = ("relu_9", "relu_15")
+
+
+def _tap_index(name, arg="remd_taps"):
     if name not in _TAPS:
-        raise ValueError(f"remd_taps: {name!r} is not a tap of the loss network {_TAPS}")
+        raise ValueError(f"{arg}: {name!r} is not a tap of the loss network {_TAPS}")
     return _TAPS.index(name)
 
 
 def default_args(**kw):
     a = dict(train_iter=10, batch_size=8, lr=2e-4, content_lam=1.25, style_lam=0.5, tv_lam=0.0006, lf_lam=1.0,
              org_img_lam=0.5, save_dir="models/ast/", load=False, image_size=512, full_losses=False,
-             remd_lam=0.0, remd_taps=REMD_TAPS)
+             remd_lam=0.0, remd_taps=REMD_TAPS, selfsim_lam=0.0, selfsim_taps=SELFSIM_TAPS)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -224,6 +233,13 @@ class AdaINTrainer:
             mean_terms = mean_terms + remd_lam * remd_loss
             loss = loss + remd_lam * remd_loss
             out.update(loss=loss, remd_loss=remd_loss)
+        selfsim_lam = float(getattr(a, "selfsim_lam", 0.0))
+        if selfsim_lam > 0:   # the self-similarity content term; nothing is launched without it
+            ss_idx = [_tap_index(k, "selfsim_taps") for k in getattr(a, "selfsim_taps", SELFSIM_TAPS)]
+            selfsim_loss = torch.stack([L.compute_selfsim_loss(s_taps[i], taps[i][:b]) for i in ss_idx]).sum()
+            mean_terms = mean_terms + selfsim_lam * selfsim_loss
+            loss = loss + selfsim_lam * selfsim_loss
+            out.update(loss=loss, selfsim_loss=selfsim_loss)
         if getattr(a, "full_losses", False):
             org_out = self.net.decoder(f_c)
             o_taps = self.lossnet(org_out)

@@ -568,6 +568,79 @@ int ast_remd_loss_backward_f32(const float* x, const float* y, const float* inv_
                                float* dx, int n, int ns, int c, int m, int p, float weight, void* workspace,
                                long long workspace_bytes, void* stream);
 
+/* Self-similarity content loss (Kolkin et al., STROTSS, CVPR 2019; csrc/selfsim.hip; an extension, no
+ * reference counterpart): the pattern of pairwise cosine distances inside the stylised map is asked to
+ * equal the pattern inside the content map, exact (every pixel pair takes part, nothing is sampled),
+ * with a backward to the stylised map.
+ * Inputs, fp32 dense NCHW with the spatial sides flattened: x [n, c, pixels], the differentiable side,
+ * and cmap of the same shape. N = pixels. Limits: c in 1..AST_REMD_MAX_C, pixels in
+ * 1..AST_SELFSIM_MAX_PIXELS, n <= 65535. Per sample, for either map f:
+ * Inverse norm: u_i = 1 / ||f_i||_2, exactly 0 unless the squared norm is positive: ast_cosine_norms_f32.
+ * Distance: D_f(i, j) = 1 - <f_i, f_j> (u_i u_j) for i != j and D_f(i, i) = 0 by definition (it is not
+ * computed as 1 - ||fh||^2). The inner product is one fp32 fma chain over the channels in a fixed order:
+ * its bits depend on the two vectors only, not on which tile either falls in, and D_f(i, j) = D_f(j, i)
+ * in bits. A zero vector is at distance 1 from every other pixel.
+ * Column sum: r_f(j) = sum_i D_f(i, j), computed as (N - 1) - (<fh_j, S> - ||fh_j||^2) with fh = u f and
+ * S = sum_i fh_i, each sum in a fixed order. q_f(j) = 1 / r_f(j) when r_f(j) is positive and finite, else
+ * 0: a map of one pixel gives q = 0, loss 0 and gradient 0.
+ * Difference: e(i, j) = D_x(i, j) q_x(j) - D_c(i, j) q_c(j), the two products rounded on their own (equal
+ * maps give exactly 0); s(i, j) = +1 / -1 / 0 for e > 0 / < 0 / otherwise: e == 0, a NaN and the diagonal
+ * give 0.
+ * Loss: L_b = (1 / N) sum_{i != j} |e(i, j)|, in [0, 2]; sums[b] = L_b; *loss += weight / n * sum_b L_b,
+ * the samples in a fixed order. loss is a loss accumulator (AST_LOSS_ACC_FLOATS floats, above).
+ * Column signed sum: t(j) = q_x(j) sum_{k != j} s(k, j) D_x(k, j).
+ * Sign planes: pos and neg, int64 [n, N, ceil(N / 64)]: bit k of word (i, J) is set in pos when
+ * s(i, 64 J + k) = +1 and in neg when it is -1. Diagonal bits and bits past N are 0.
+ * Backward, to x only (cmap is data, and is not read). With g = *grad_scale (a device scalar), xh = u x:
+ *   W(m, j) = (s(m, j) - t(j)) q_x(j) + (s(j, m) - t(m)) q_x(m)        (m != j; symmetric)
+ *   G_m     = sum_{j != m} W(m, j) u_j x_j      (j ascending in pairs, the MFMA's order)
+ *   dxh_m   = -(g weight / (n N)) G_m
+ *   dx_m    = u_m (dxh_m - xh_m <xh_m, dxh_m>), exactly 0 where u_m = 0
+ * No cosine is recomputed: the planes cost N^2 / 4 bytes per sample. Every element of dx is written once.
+ * Stages and their composition: ast_selfsim_loss_f32 is ast_cosine_norms_f32 on x, on cmap,
+ * ast_selfsim_colsum_f32 on x, on cmap, ast_selfsim_pairs_f32 and ast_selfsim_total_f32, bit for bit.
+ * Workspaces are device memory, 256-byte aligned, of at least the matching *_workspace_bytes query. No
+ * floating-point atomics, no host synchronisation, no allocation; a non-finite value stays inside its
+ * own sample.
+ * AST_E_NULLPTR: a null pointer. AST_E_SHAPE: a size <= 0 or over the limits above, a short workspace.
+ * AST_E_UNSUPPORTED: c > AST_REMD_MAX_C. The queries return the same negative codes. All checks run
+ * before the first launch. */
+#define AST_SELFSIM_MAX_PIXELS 16384
+
+/* col_sum [n, pixels] = r_f of x [n, c, pixels] and its inverse norms; two launches. Workspace: the
+ * channel sums S, 4 n c bytes and alignment. */
+long long ast_selfsim_colsum_workspace_bytes(int n, int c);
+int ast_selfsim_colsum_f32(const float* x, const float* inv_norm, float* col_sum, int n, int c, int pixels,
+                           void* workspace, long long workspace_bytes, void* stream);
+
+/* sums [n], t [n, pixels] and the planes from the maps, their inverse norms and column sums: one
+ * workgroup per pair (I <= J) of 64-pixel tiles, 2 N^2 c FLOP per sample, then the merge of t in tile
+ * order and the per-sample sum. Workspace: one partial of t per (tile, pixel) and one loss partial per
+ * tile pair: 4 n (ceil(N / 64) N + pairs) bytes and alignment. */
+long long ast_selfsim_pairs_workspace_bytes(int n, int pixels);
+int ast_selfsim_pairs_f32(const float* x, const float* cmap, const float* inv_x, const float* inv_c,
+                          const float* r_x, const float* r_c, float* sums, float* t, long long* pos,
+                          long long* neg, int n, int c, int pixels, void* workspace,
+                          long long workspace_bytes, void* stream);
+
+/* *loss += weight / n * sum_b sums[b]; one workgroup. */
+int ast_selfsim_total_f32(const float* sums, float* loss, int n, float weight, void* stream);
+
+/* The whole forward; inv_x, r_x, t, pos and neg are what the backward reads. */
+long long ast_selfsim_loss_workspace_bytes(int n, int c, int pixels);
+int ast_selfsim_loss_f32(const float* x, const float* cmap, float* inv_x, float* inv_c, float* r_x,
+                         float* r_c, float* t, long long* pos, long long* neg, float* sums, float* loss,
+                         int n, int c, int pixels, float weight, void* workspace,
+                         long long workspace_bytes, void* stream);
+
+/* dx [n, c, pixels] from the forward's outputs: the GEMM of W' with x (2 N^2 c FLOP per sample) into
+ * the workspace, then the normalisation backward. Workspace: G, 4 n c pixels bytes and alignment. */
+long long ast_selfsim_loss_backward_workspace_bytes(int n, int c, int pixels);
+int ast_selfsim_loss_backward_f32(const float* x, const float* inv_x, const float* r_x, const float* t,
+                                  const long long* pos, const long long* neg, const float* grad_scale,
+                                  float* dx, int n, int c, int pixels, float weight, void* workspace,
+                                  long long workspace_bytes, void* stream);
+
 /* Feature k-means and the label mode filter (csrc/kmeans.hip; an extension, no reference counterpart):
  * the stage that makes the uint8 label maps of the regional transforms above from the features
  * themselves, as Multimodal Style Transfer (Zhang et al., ICCV 2019) clusters the style's relu4_1
