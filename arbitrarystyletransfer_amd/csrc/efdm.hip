@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "sort.h"
+#include "ws.h"
 
 using namespace ast_sort;
 
@@ -188,8 +189,6 @@ int64_t pow2_padded(int64_t m) {   // the LDS sort length of m <= AST_EFDM_FUSED
 
 int sort_threads(int64_t P) { return (int)(P / kE < kMaxThreads ? P / kE : kMaxThreads); }
 
-int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
-
 bool chunk_ok(int chunk) {   // 0: automatic; else a power of two in 64..AST_EFDM_FUSED_MAX
   return chunk == 0 || (chunk >= 64 && chunk <= AST_EFDM_FUSED_MAX && (chunk & (chunk - 1)) == 0);
 }
@@ -244,9 +243,31 @@ bool efdm_fused(int64_t mc, int64_t ms, int chunk) {
   return chunk == 0 && mc <= AST_EFDM_FUSED_MAX && ms <= AST_EFDM_FUSED_MAX;
 }
 
-int64_t efdm_ws_bytes(int64_t n, int64_t ns, int64_t c, int64_t mc, int64_t ms) {
-  // content keys and indices, style keys, two buffers each (the merge passes ping-pong)
-  return 4 * al256(4 * n * c * mc) + 2 * al256(4 * ns * c * ms);
+// The general-path sort's workspace: [keys | keys | indices | indices], two buffers each (the merge
+// passes ping-pong); the indices only when wanted
+struct SortWs {
+  uint32_t* key[2];
+  int* idx[2];
+  int64_t bytes;
+};
+
+SortWs sort_ws(void* base, int64_t planes, int64_t m, bool want_index) {
+  ast_ws::Walk wk(base);
+  const int64_t b = 4 * planes * m;
+  return {{wk.take<uint32_t>(b), wk.take<uint32_t>(b)},
+          {want_index ? wk.take<int>(b) : nullptr, want_index ? wk.take<int>(b) : nullptr}, wk.off};
+}
+
+// The general path's workspace: [the content's sort with indices | the style's sort]
+struct EfdmWs {
+  void *content, *style;
+  int64_t bytes;
+};
+
+EfdmWs efdm_ws(void* base, int64_t planes, int64_t splanes, int64_t mc, int64_t ms) {
+  ast_ws::Walk wk(base);
+  return {wk.take<void>(sort_ws(nullptr, planes, mc, true).bytes),
+          wk.take<void>(sort_ws(nullptr, splanes, ms, false).bytes), wk.off};
 }
 
 // planes of m elements: both counts positive and within 2^31 - 1, at most 2^40 elements in all (the
@@ -268,7 +289,7 @@ long long ast_efdm_ex_workspace_bytes(int n, int ns, int c, long long mc, long l
   if (!efdm_shape_ok(n, ns, c, mc, ms)) return AST_E_SHAPE;
   if (!chunk_ok(chunk)) return AST_E_UNSUPPORTED;
   if (efdm_fused(mc, ms, chunk)) return 0;
-  return efdm_ws_bytes(n, ns, c, mc, ms);
+  return efdm_ws(nullptr, (int64_t)n * c, (int64_t)ns * c, mc, ms).bytes;
 }
 
 long long ast_efdm_workspace_bytes(int n, int ns, int c, long long mc, long long ms) {
@@ -302,18 +323,16 @@ int ast_efdm_ex_f32(const float* content, const float* style, float* out, int n,
 
   if (chunk == 0) chunk = kAutoChunk;
   if (!workspace) return AST_E_NULLPTR;
-  if (workspace_bytes < efdm_ws_bytes(n, ns, c, mc, ms)) return AST_E_SHAPE;
+  const EfdmWs w = efdm_ws(workspace, planes, splanes, mc, ms);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   if (((uintptr_t)workspace & 3) != 0) return AST_E_UNSUPPORTED;
   if (!general_fits(planes, mc, chunk) || !general_fits(splanes, ms, chunk)) return AST_E_SHAPE;
-  unsigned char* wsb = (unsigned char*)workspace;
-  const int64_t cb = al256(4 * planes * mc), sb = al256(4 * splanes * ms);
+  const SortWs wc_ = sort_ws(w.content, planes, mc, true), ws_ = sort_ws(w.style, splanes, ms, false);
   uint32_t *ck = nullptr, *sk = nullptr;
   int *ci = nullptr, *si = nullptr;
-  int e = sort_general<true>(content, planes, mc, chunk, (uint32_t*)wsb, (uint32_t*)(wsb + cb), (int*)(wsb + 2 * cb),
-                             (int*)(wsb + 3 * cb), st, &ck, &ci);
+  int e = sort_general<true>(content, planes, mc, chunk, wc_.key[0], wc_.key[1], wc_.idx[0], wc_.idx[1], st, &ck, &ci);
   if (e) return e;
-  e = sort_general<false>(style, splanes, ms, chunk, (uint32_t*)(wsb + 4 * cb), (uint32_t*)(wsb + 4 * cb + sb),
-                          nullptr, nullptr, st, &sk, &si);
+  e = sort_general<false>(style, splanes, ms, chunk, ws_.key[0], ws_.key[1], nullptr, nullptr, st, &sk, &si);
   if (e) return e;
   const int64_t bps = (mc + kMergeThreads - 1) / kMergeThreads;
   hipLaunchKernelGGL(efdm_scatter_kernel, dim3((unsigned)(planes * bps)), dim3(kMergeThreads), 0, st, content,
@@ -330,7 +349,7 @@ long long ast_plane_sort_workspace_bytes(long long planes, long long m, int want
   if (!planes_ok(planes, m)) return AST_E_SHAPE;
   if (!chunk_ok(chunk)) return AST_E_UNSUPPORTED;
   if (chunk == 0 && m <= AST_EFDM_FUSED_MAX) return 0;
-  return (want_index ? 4 : 2) * al256(4 * planes * m);
+  return sort_ws(nullptr, planes, m, want_index != 0).bytes;
 }
 
 int ast_plane_sort_f32(const float* x, float* sorted, int* index_or_null, long long planes, long long m, int chunk,
@@ -358,17 +377,14 @@ int ast_plane_sort_f32(const float* x, float* sorted, int* index_or_null, long l
 
   if (chunk == 0) chunk = kAutoChunk;
   if (!workspace) return AST_E_NULLPTR;
-  const int64_t b = al256(4 * planes * m);
-  if (workspace_bytes < (want_index ? 4 : 2) * b) return AST_E_SHAPE;
+  const SortWs w = sort_ws(workspace, planes, m, want_index);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   if (((uintptr_t)workspace & 3) != 0) return AST_E_UNSUPPORTED;
   if (!general_fits(planes, m, chunk)) return AST_E_SHAPE;
-  unsigned char* wsb = (unsigned char*)workspace;
   uint32_t* kr = nullptr;
   int* ir = nullptr;
-  int e = want_index ? sort_general<true>(x, planes, m, chunk, (uint32_t*)wsb, (uint32_t*)(wsb + b),
-                                          (int*)(wsb + 2 * b), (int*)(wsb + 3 * b), st, &kr, &ir)
-                     : sort_general<false>(x, planes, m, chunk, (uint32_t*)wsb, (uint32_t*)(wsb + b), nullptr, nullptr,
-                                           st, &kr, &ir);
+  int e = want_index ? sort_general<true>(x, planes, m, chunk, w.key[0], w.key[1], w.idx[0], w.idx[1], st, &kr, &ir)
+                     : sort_general<false>(x, planes, m, chunk, w.key[0], w.key[1], nullptr, nullptr, st, &kr, &ir);
   if (e) return e;
   const int64_t total = planes * m;
   const int64_t want = (total + kMergeThreads - 1) / kMergeThreads;

@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "sort.h"
+#include "ws.h"
 
 using namespace ast_sort;
 
@@ -261,8 +262,6 @@ int pow2_padded(int64_t m) {   // the LDS sort length of m <= AST_EFDM_FUSED_MAX
 
 int sort_threads(int P) { return P / kE < kMaxThreads ? P / kE : kMaxThreads; }
 
-int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
-
 size_t bank_lds(int P, bool lab) { return lab ? (size_t)6 * P + kScanBytes : (size_t)4 * P; }
 
 size_t apply_lds(int P) { return (size_t)6 * P + kScanBytes + kTableBytes; }
@@ -305,6 +304,18 @@ int allow_bank_sort(int m, bool lab) {
   return lab ? allow_lds(bank_sort_kernel<true>, lds) : allow_lds(bank_sort_kernel<false>, lds);
 }
 
+// The whole op's workspace: [sorted bank | region counts of the bank]
+struct RegionsWs {
+  float* bank;
+  int* count;
+  int64_t bytes;
+};
+
+RegionsWs regions_ws(void* base, int c, int regions, int styles, int hs, int ws) {
+  ast_ws::Walk wk(base);
+  return {wk.take<float>((int64_t)4 * styles * c * hs * ws), wk.take<int>((int64_t)4 * styles * regions), wk.off};
+}
+
 }  // namespace
 
 extern "C" {
@@ -322,8 +333,7 @@ int ast_efdm_region_sort_f32(const float* x, const unsigned char* labels_or_null
 
 long long ast_efdm_regions_workspace_bytes(int n, int c, int hc, int wc, int regions, int styles, int hs, int ws) {
   const int e = regions_check(n, c, hc, wc, regions, styles, hs, ws);
-  if (e) return e;
-  return al256((int64_t)4 * styles * c * hs * ws) + al256((int64_t)4 * styles * regions);
+  return e ? e : regions_ws(nullptr, c, regions, styles, hs, ws).bytes;
 }
 
 int ast_efdm_regions_f32(const float* content, const unsigned char* labels, const float* styles,
@@ -334,7 +344,8 @@ int ast_efdm_regions_f32(const float* content, const unsigned char* labels, cons
   int e = regions_check(n, c, hc, wc, regions, s, hs, ws);
   if (e) return e;
   if (mix_n != 1 && mix_n != n) return AST_E_SHAPE;
-  if (workspace_bytes < ast_efdm_regions_workspace_bytes(n, c, hc, wc, regions, s, hs, ws)) return AST_E_SHAPE;
+  const RegionsWs w = regions_ws(workspace, c, regions, s, hs, ws);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   if (((uintptr_t)workspace & 3) != 0) return AST_E_UNSUPPORTED;
   const int mc = hc * wc, ms = hs * ws;
   const int pc = pow2_padded(mc);
@@ -346,12 +357,10 @@ int ast_efdm_regions_f32(const float* content, const unsigned char* labels, cons
   e = allow_lds(efdm_regions_kernel, lds);
   if (e) return e;
   hipStream_t st = (hipStream_t)stream;
-  float* bank = (float*)workspace;
-  int* count = (int*)((unsigned char*)workspace + al256((int64_t)4 * s * c * ms));
-  e = launch_bank_sort(styles, style_labels_or_null, bank, count, s, c, ms, regions, st);
+  e = launch_bank_sort(styles, style_labels_or_null, w.bank, w.count, s, c, ms, regions, st);
   if (e) return e;
   hipLaunchKernelGGL(efdm_regions_kernel, dim3((unsigned)((int64_t)n * c)), dim3(sort_threads(pc)), lds, st, content,
-                     labels, (const float*)bank, (const int*)count, mix, out, c, mc, pc, ms, regions, s,
+                     labels, (const float*)w.bank, (const int*)w.count, mix, out, c, mc, pc, ms, regions, s,
                      mix_n == 1 ? 0 : regions * s, regional ? 1 : 0, (float)alpha, alpha == 1.0 ? 1 : 0);
   return (int)hipGetLastError();
 }

@@ -33,8 +33,12 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "match_tile.h"
+#include "ws.h"
 
 namespace {
+
+using ast_tile::fold_arg;
 
 constexpr int kT = 256;            // threads per workgroup everywhere in this file
 constexpr int kMaxK = AST_KMEANS_MAX_K;
@@ -67,14 +71,6 @@ __host__ __device__ constexpr bool adds(int mode) { return mode == UPDATE || mod
 // floats of dynamic LDS: [centroids C x NK | tile image C x (TP + 1) | partial distances (256 / TP) x NK x TP | labels TP]
 __host__ __device__ constexpr int64_t lds_floats(int mode, int tp, int nk, int c) {
   return (scores(mode) ? (int64_t)nk * c + (int64_t)kT * nk : 0) + (adds(mode) ? (int64_t)c * (tp + 1) : 0) + tp;
-}
-
-// b wins over a: greater, or equal with the lower index
-__device__ __forceinline__ void fold_max(float& v, int& ix, float ov, int oi) {
-  if (ov > v || (ov == v && oi < ix)) {
-    v = ov;
-    ix = oi;
-  }
 }
 
 extern __shared__ __attribute__((aligned(16))) float km_smem[];
@@ -178,9 +174,9 @@ __global__ __launch_bounds__(kT) void kmeans_tile_kernel(const TileArgs a) {
         for (int o = 32; o > 0; o >>= 1) {
           const float ov = __shfl_xor(v, o, 64);
           const int oi = __shfl_xor(ix, o, 64);
-          fold_max(v, ix, ov, oi);
+          fold_arg<true>(v, ix, ov, oi);
         }
-        fold_max(bestv, besti, v, ix);
+        fold_arg<true>(bestv, besti, v, ix);
       } else {
         if (tid < TP) labs[tid] = valid ? lab : 255;
         if constexpr (MODE != UPDATE)
@@ -260,7 +256,7 @@ __global__ __launch_bounds__(kT) void kmeans_reduce_kernel(const float* __restri
   sh[q][lane] = s;
   const int n = count_sum(pcnt, nwg, K, k, shc);   // its barrier covers sh too
   if (q == 0 && ch < C) {
-    const float tot = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+    const float tot = ast_tile::quarter_sum(sh, lane);
     const int64_t o = (int64_t)k * C + ch;
     cen[o] = n > 0 ? tot / (float)n : prev[o];
   }
@@ -283,12 +279,12 @@ __global__ __launch_bounds__(kT) void kmeans_argmax_kernel(const float* __restri
   __shared__ int shi[4];
   float v = -INFINITY;
   int ix = INT_MAX;
-  for (int w = threadIdx.x; w < nwg; w += kT) fold_max(v, ix, pval[w], pidx[w]);
+  for (int w = threadIdx.x; w < nwg; w += kT) fold_arg<true>(v, ix, pval[w], pidx[w]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(v, o, 64);
     const int oi = __shfl_xor(ix, o, 64);
-    fold_max(v, ix, ov, oi);
+    fold_arg<true>(v, ix, ov, oi);
   }
   if ((threadIdx.x & 63) == 0) {
     shv[threadIdx.x >> 6] = v;
@@ -296,7 +292,7 @@ __global__ __launch_bounds__(kT) void kmeans_argmax_kernel(const float* __restri
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int q = 1; q < 4; ++q) fold_max(v, ix, shv[q], shi[q]);
+    for (int q = 1; q < 4; ++q) fold_arg<true>(v, ix, shv[q], shi[q]);
     *seed = ix == INT_MAX ? 0 : ix;
   }
 }
@@ -352,8 +348,6 @@ __global__ __launch_bounds__(kT) void label_mode_kernel(const uint8_t* __restric
 // ------------------------------------------------------------------------------------------------
 // Host side: argument checks, workspace layout, launch sequences
 // ------------------------------------------------------------------------------------------------
-
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 // AST_OK, or the code that rejects a bank [b, c, h, w] and k clusters
 inline int bank_shape(int b, int c, int h, int w, int k) {
@@ -441,16 +435,16 @@ inline Ws ws_of(unsigned char* base, int b, int c, int h, int w, int k) {
   // the seeding runs with one centroid, so with a plan of its own: size for the larger grid
   const Plan pk = plan_of(b, c, h, w, k), p1 = plan_of(b, c, h, w, 1);
   const int64_t g = pk.grid > p1.grid ? pk.grid : p1.grid;
+  ast_ws::Walk wk(base);
   Ws s;
-  int64_t o = 0;
-  s.part = (float*)(base + o), o += al256(4 * g * k * c);
-  s.pcnt = (int*)(base + o), o += al256((int64_t)4 * pk.wide_grid * k);   // wide_grid >= grid
-  s.dmin = (float*)(base + o), o += al256((int64_t)4 * b * h * w);
-  s.pval = (float*)(base + o), o += al256((int64_t)4 * p1.wide_grid);
-  s.pidx = (int*)(base + o), o += al256((int64_t)4 * p1.wide_grid);
-  s.mean = (float*)(base + o), o += al256(4 * c);
-  s.seeds = (int*)(base + o), o += al256(4 * kMaxK);
-  s.bytes = o;
+  s.part = wk.take<float>(4 * g * k * c);
+  s.pcnt = wk.take<int>((int64_t)4 * pk.wide_grid * k);   // wide_grid >= grid
+  s.dmin = wk.take<float>((int64_t)4 * b * h * w);
+  s.pval = wk.take<float>((int64_t)4 * p1.wide_grid);
+  s.pidx = wk.take<int>((int64_t)4 * p1.wide_grid);
+  s.mean = wk.take<float>(4 * c);
+  s.seeds = wk.take<int>(4 * kMaxK);
+  s.bytes = wk.off;
   return s;
 }
 
@@ -596,7 +590,7 @@ long long ast_label_mode_filter_workspace_bytes(int n, int h, int w, int passes)
   const int e = map_shape(n, h, w);
   if (e) return e;
   if (passes < 0) return AST_E_UNSUPPORTED;
-  return passes > 1 ? al256((int64_t)n * h * w) : 0;
+  return passes > 1 ? ast_ws::al256((int64_t)n * h * w) : 0;
 }
 
 int ast_label_mode_filter_u8(const unsigned char* labels, unsigned char* out, int n, int h, int w, int regions,

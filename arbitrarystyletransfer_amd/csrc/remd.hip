@@ -43,20 +43,25 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "match_tile.h"
 #include "wave.h"
+#include "ws.h"
 
 namespace {
 
+using ast_tile::acc_row;
+using ast_tile::f32x16;
+using ast_tile::fold_arg;
+using ast_tile::stage_load;
+using ast_tile::stage_store;
 using ast_wave::block_sum;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kT = 256;   // threads per workgroup everywhere in this file
 constexpr int MT = 64;    // pixels per tile side (4 waves x 32 x 32)
 constexpr int KC = 64;    // channels per staged chunk
 constexpr int RT = KC / 4;  // channel runs per wave and chunk
 constexpr int kMaxC = AST_REMD_MAX_C;
 constexpr int kMaxPixels = AST_REMD_MAX_PIXELS;  // 4 * KC * pixels stays below 2^31: the buffer offsets are int32
-constexpr int kMaxSplits = 64;
 constexpr int kTargetWGs = 8 * 256;
 constexpr int kMinSplitTiles = 4;  // a split of fewer style tiles does not amortise its content tile's loads
 constexpr int GC = 32;    // channels per workgroup of the row gather
@@ -73,15 +78,11 @@ __global__ __launch_bounds__(kT) void remd_invnorm_kernel(const float* __restric
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6, p = blockIdx.x * 64 + lane;
   const float* X = x + (int64_t)blockIdx.y * C * hw;
   float s = 0.f;
-  if (p < hw)
-    for (int c = g; c < C; c += 4) {
-      const float v = X[(int64_t)c * hw + p];
-      s = fmaf(v, v, s);
-    }
+  if (p < hw) s = ast_tile::quarter_sqsum(X, C, hw, g, p);
   sh[g][lane] = s;
   __syncthreads();
   if (g == 0 && p < hw) {
-    const float t = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+    const float t = ast_tile::quarter_sum(sh, lane);
     const float q = 1.0f / sqrtf(t);
     inv[(int64_t)blockIdx.y * hw + p] = (t > 0.f && q > 0.f) ? q : 0.f;
   }
@@ -91,32 +92,7 @@ __global__ __launch_bounds__(kT) void remd_invnorm_kernel(const float* __restric
 // Match
 // ------------------------------------------------------------------------------------------------
 
-// The chunk whose first channel plane is `chunk` (`cleft` >= 1 channels are left from there) into
-// registers: wave w takes channels w, w + 4, ... of the chunk, lane l pixel p0 + l. Buffer loads
-// whose descriptor ends with the chunk's last real channel: a channel past C reads as 0 (the
-// hardware's range check), and so does anything past the sample. A pixel past the map reads the next
-// channel's first pixels; such a row or column of the tile is never folded.
-__device__ __forceinline__ void stage_load(float (&reg)[RT], const float* chunk, int cleft, int hw, int p0, int wave,
-                                           int lane) {
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(chunk), 0, 4 * min(cleft, KC) * hw, 0x00020000);
-#pragma unroll
-  for (int t = 0; t < RT; ++t)
-    reg[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, 4 * ((wave + 4 * t) * hw + p0 + lane), 0, 0));
-}
-
-__device__ __forceinline__ void stage_store(const float (&reg)[RT], float* S, int wave, int lane) {
-#pragma unroll
-  for (int t = 0; t < RT; ++t) S[(wave + 4 * t) * MT + lane] = reg[t];
-}
-
-// o wins over the running pair: less, or equal with the lower index
-__device__ __forceinline__ void fold_min(float& v, int& ix, float ov, int oi) {
-  if (ov < v || (ov == v && oi < ix)) {
-    v = ov;
-    ix = oi;
-  }
-}
+// stage_load / stage_store (match_tile.h): a chunk of KC channels x 64 pixels into registers, then LDS.
 
 // grid (content tiles, splits, samples). Row pairs of sample b and split s at [(b * splits + s) * M + i]:
 // the outputs themselves when splits == 1. Column pairs of content tile t at [(b * tiles + t) * P + j];
@@ -142,12 +118,12 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
   const float* Ar = As + h * MT + wm * 32 + r;
   const float* Br = Bs + h * MT + wn * 32 + r;
 
-  // the lane's 16 accumulator rows: content pixel m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h
+  // the lane's 16 accumulator rows: content pixel m0 + wm * 32 + acc_row(i, h)
   float ur[16], best[16];
   int bidx[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int gi = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+    const int gi = m0 + wm * 32 + acc_row(i, h);
     ur[i] = gi < M ? ub[gi] : 0.f;
     best[i] = INFINITY;
     bidx[i] = 0;
@@ -186,7 +162,7 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
     int cix = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int gi = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int gi = m0 + wm * 32 + acc_row(i, h);
       const float d = 1.0f - (acc[i] * ur[i]) * vj;
       if (jvalid && d < best[i]) {  // j grows from tile to tile: the lowest j of equal distances stays
         best[i] = d;
@@ -198,7 +174,7 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
       }
     }
     // the column: the other lane half holds the rows in between, the wm = 1 wave the 32 rows after
-    fold_min(cmin, cix, __shfl_xor(cmin, 32, 64), __shfl_xor(cix, 32, 64));
+    fold_arg<false>(cmin, cix, __shfl_xor(cmin, 32, 64), __shfl_xor(cix, 32, 64));
     if (wm == 1 && h == 0) {
       colv[wn][r] = cmin;
       coli[wn][r] = cix;
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
     for (int o = 16; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o, 64);
       const int oi = __shfl_xor(ix, o, 64);
-      fold_min(bv, ix, ov, oi);
+      fold_arg<false>(bv, ix, ov, oi);
     }
     best[i] = bv;
     bidx[i] = ix;
@@ -234,7 +210,7 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
   if (wn == 1 && r == 0) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int row = acc_row(i, h);
       redv[wm * 32 + row] = best[i];
       redi[wm * 32 + row] = bidx[i];
     }
@@ -244,11 +220,11 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
     const int64_t ob = ((int64_t)b * gridDim.y + split) * M;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = (i & 3) + 8 * (i >> 2) + 4 * h, gi = m0 + wm * 32 + row;
+      const int row = acc_row(i, h), gi = m0 + wm * 32 + row;
       if (gi >= M) continue;
       float bv = best[i];
       int ix = bidx[i];
-      fold_min(bv, ix, redv[wm * 32 + row], redi[wm * 32 + row]);
+      fold_arg<false>(bv, ix, redv[wm * 32 + row], redi[wm * 32 + row]);
       orow[ob + gi] = bv;
       oridx[ob + gi] = ix;
     }
@@ -261,20 +237,7 @@ __global__ __launch_bounds__(kT) void remd_match_kernel(const float* __restrict_
 __global__ __launch_bounds__(kT) void remd_merge_kernel(const float* __restrict__ pmin, const int* __restrict__ pidx,
                                                        float* __restrict__ omin, int* __restrict__ oidx, int count,
                                                        int slots) {
-  const int e = blockIdx.x * kT + threadIdx.x, b = blockIdx.y;
-  if (e >= count) return;
-  float bv = INFINITY;
-  int ix = 0;
-  for (int s = 0; s < slots; ++s) {
-    const int64_t o = ((int64_t)b * slots + s) * count + e;
-    const float ov = pmin[o];
-    if (ov < bv) {
-      bv = ov;
-      ix = pidx[o];
-    }
-  }
-  omin[(int64_t)b * count + e] = bv;
-  oidx[(int64_t)b * count + e] = ix;
+  ast_tile::merge_slots<false, kT>(pmin, pidx, omin, oidx, count, slots, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -467,12 +430,9 @@ __global__ __launch_bounds__(kT) void remd_bwd_col_kernel(const float* __restric
 // Host side: argument checks, workspace layouts, launch sequences
 // ------------------------------------------------------------------------------------------------
 
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-inline int tiles_of(int64_t p) { return (int)((p + MT - 1) / MT); }
+using ast_tile::tiles_of;
 
-inline int map_shape(int n, int pixels) {
-  return (n <= 0 || n > 65535 || pixels <= 0 || pixels > kMaxPixels) ? AST_E_SHAPE : AST_OK;
-}
+inline int map_shape(int n, int pixels) { return ast_tile::map_shape(n, pixels, kMaxPixels); }
 
 inline int pair_shape(int n, int ns, int m, int p) {
   if (n <= 0 || ns <= 0 || (ns != n && ns != 1)) return AST_E_SHAPE;
@@ -480,36 +440,42 @@ inline int pair_shape(int n, int ns, int m, int p) {
   return e ? e : map_shape(ns, p);
 }
 
-inline int chan_shape(int c) { return c <= 0 ? AST_E_SHAPE : c > kMaxC ? AST_E_UNSUPPORTED : AST_OK; }
+inline int chan_shape(int c) { return ast_tile::chan_shape(c, kMaxC); }
 
-// Splits of the style tiles, after swap.hip: as asked (clamped to the tiles and to 64), or, for 0, as
+// The match's workspace: [column partial minima | column partial indices | row partial minima | row
+// partial indices], the column partials per content tile, the row partials per split and only when
+// there is more than one. Splits of the style tiles (ast_tile::split_tiles): as asked, or, for 0, as
 // many as bring the grid to about 8 workgroups per CU while a split keeps at least 4 tiles (measured at
-// C = 512, n = 16: 2 splits at 64 x 64, 4 at 32 x 32); then rounded so that no split is empty.
-inline int match_splits(int n, int m, int p, int want, int* tiles_per_split) {
-  const int64_t wgs = (int64_t)n * tiles_of(m);
-  const int ntiles = tiles_of(p);
-  int64_t s = want > 0 ? want : (kTargetWGs + wgs - 1) / wgs;
-  if (want <= 0 && s > ntiles / kMinSplitTiles) s = ntiles / kMinSplitTiles;
-  if (s > kMaxSplits) s = kMaxSplits;
-  if (s > ntiles) s = ntiles;
-  if (s < 1) s = 1;
-  const int tps = (int)((ntiles + s - 1) / s);
-  if (tiles_per_split) *tiles_per_split = tps;
-  return (ntiles + tps - 1) / tps;
+// C = 512, n = 16: 2 splits at 64 x 64, 4 at 32 x 32).
+struct MatchWs {
+  int splits, tiles_per_split;
+  float* pcol;
+  int* pcidx;
+  float* prow;  // null for one split: the rows go straight to the outputs
+  int* pridx;
+  int64_t bytes;
+};
+
+inline MatchWs match_ws(void* base, int n, int m, int p, int want) {
+  ast_ws::Walk wk(base);
+  int tps = 0;
+  const int s = ast_tile::split_tiles((int64_t)n * tiles_of(m), tiles_of(p), want, kTargetWGs, kMinSplitTiles, &tps);
+  const int64_t col = (int64_t)4 * n * tiles_of(m) * p, row = (int64_t)4 * n * s * m;
+  return {s, tps, wk.take<float>(col), wk.take<int>(col), s > 1 ? wk.take<float>(row) : nullptr,
+          s > 1 ? wk.take<int>(row) : nullptr, wk.off};
 }
 
-// [column partial minima | column partial indices | row partial minima | row partial indices]
-inline int64_t col_part_bytes(int n, int m, int p) { return al256((int64_t)4 * n * tiles_of(m) * p); }
-inline int64_t row_part_bytes(int n, int m, int s) { return s > 1 ? al256((int64_t)4 * n * s * m) : 0; }
-inline int64_t match_ws(int n, int m, int p, int want) {
-  const int s = match_splits(n, m, p, want, nullptr);
-  return 2 * col_part_bytes(n, m, p) + 2 * row_part_bytes(n, m, s);
-}
+// The backward's workspace: [start | cursor | list]
+struct BwdWs {
+  int *start, *cursor, *list;
+  int64_t bytes;
+};
 
-// [start | cursor | list]
-inline int64_t start_bytes(int n, int m) { return al256((int64_t)4 * n * (m + 1)); }
-inline int64_t cursor_bytes(int n, int m) { return al256((int64_t)4 * n * m); }
-inline int64_t bwd_ws(int n, int m, int p) { return start_bytes(n, m) + cursor_bytes(n, m) + al256((int64_t)4 * n * p); }
+inline BwdWs bwd_ws(void* base, int n, int m, int p) {
+  ast_ws::Walk wk(base);
+  return {wk.take<int>((int64_t)4 * n * (m + 1)), wk.take<int>((int64_t)4 * n * m), wk.take<int>((int64_t)4 * n * p),
+          wk.off};
+}
 
 int norms_launch(const float* x, float* inv, int n, int c, int hw, hipStream_t st) {
   hipLaunchKernelGGL(remd_invnorm_kernel, dim3((hw + 63) / 64, n), dim3(kT), 0, st, x, inv, c, hw);
@@ -517,14 +483,13 @@ int norms_launch(const float* x, float* inv, int n, int c, int hw, hipStream_t s
 }
 
 int match_launch(const float* x, const float* y, const float* u, const float* v, float* rmin, int* ridx, float* cmin,
-                 int* cidx, int n, int ns, int c, int m, int p, int want, unsigned char* wsp, hipStream_t st) {
-  int tps = 0;
-  const int splits = match_splits(n, m, p, want, &tps), ct = tiles_of(m);
-  const int64_t cb = col_part_bytes(n, m, p), rb = row_part_bytes(n, m, splits);
-  float* pc = (float*)wsp;
-  int* pci = (int*)(wsp + cb);
-  float* pr = splits > 1 ? (float*)(wsp + 2 * cb) : rmin;
-  int* pri = splits > 1 ? (int*)(wsp + 2 * cb + rb) : ridx;
+                 int* cidx, int n, int ns, int c, int m, int p, int want, void* wsp, hipStream_t st) {
+  const MatchWs w = match_ws(wsp, n, m, p, want);
+  const int splits = w.splits, tps = w.tiles_per_split, ct = tiles_of(m);
+  float* pc = w.pcol;
+  int* pci = w.pcidx;
+  float* pr = splits > 1 ? w.prow : rmin;
+  int* pri = splits > 1 ? w.pridx : ridx;
   hipLaunchKernelGGL(remd_match_kernel, dim3(ct, splits, n), dim3(kT), 0, st, x, y, u, v, pr, pri, pc, pci, c, m, p, ns,
                      tps);
   if (splits > 1)
@@ -559,7 +524,7 @@ long long ast_cosine_match_workspace_bytes(int n, int ns, int m, int p, int spli
   const int e = pair_shape(n, ns, m, p);
   if (e) return e;
   if (splits < 0) return AST_E_UNSUPPORTED;
-  return match_ws(n, m, p, splits);
+  return match_ws(nullptr, n, m, p, splits).bytes;
 }
 
 int ast_cosine_match_f32(const float* x, const float* y, const float* inv_x, const float* inv_y, float* row_min,
@@ -571,9 +536,9 @@ int ast_cosine_match_f32(const float* x, const float* y, const float* inv_x, con
   if (!e) e = chan_shape(c);
   if (e) return e;
   if (splits < 0) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < match_ws(n, m, p, splits)) return AST_E_SHAPE;
-  return match_launch(x, y, inv_x, inv_y, row_min, row_index, col_min, col_index, n, ns, c, m, p, splits,
-                      (unsigned char*)workspace, (hipStream_t)stream);
+  if (workspace_bytes < match_ws(nullptr, n, m, p, splits).bytes) return AST_E_SHAPE;
+  return match_launch(x, y, inv_x, inv_y, row_min, row_index, col_min, col_index, n, ns, c, m, p, splits, workspace,
+                      (hipStream_t)stream);
 }
 
 int ast_remd_means_f32(const float* row_min, const float* col_min, float* row_mean, float* col_mean,
@@ -589,7 +554,7 @@ int ast_remd_means_f32(const float* row_min, const float* col_min, float* row_me
 
 long long ast_remd_loss_workspace_bytes(int n, int ns, int m, int p) {
   const int e = pair_shape(n, ns, m, p);
-  return e ? e : match_ws(n, m, p, 0);
+  return e ? e : match_ws(nullptr, n, m, p, 0).bytes;
 }
 
 int ast_remd_loss_f32(const float* x, const float* y, float* inv_x, float* inv_y, float* row_min, int* row_index,
@@ -603,21 +568,20 @@ int ast_remd_loss_f32(const float* x, const float* y, float* inv_x, float* inv_y
   if (!e) e = chan_shape(c);
   if (e) return e;
   if (force_branch < 0 || force_branch > 2) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < match_ws(n, m, p, 0)) return AST_E_SHAPE;
+  if (workspace_bytes < match_ws(nullptr, n, m, p, 0).bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   e = norms_launch(x, inv_x, n, c, m, st);
   if (e) return e;
   e = norms_launch(y, inv_y, ns, c, p, st);
   if (e) return e;
-  e = match_launch(x, y, inv_x, inv_y, row_min, row_index, col_min, col_index, n, ns, c, m, p, 0,
-                   (unsigned char*)workspace, st);
+  e = match_launch(x, y, inv_x, inv_y, row_min, row_index, col_min, col_index, n, ns, c, m, p, 0, workspace, st);
   if (e) return e;
   return means_launch(row_min, col_min, row_mean, col_mean, branch, loss, n, m, p, weight, force_branch, st);
 }
 
 long long ast_remd_loss_backward_workspace_bytes(int n, int m, int p) {
   const int e = pair_shape(n, n, m, p);
-  return e ? e : bwd_ws(n, m, p);
+  return e ? e : bwd_ws(nullptr, n, m, p).bytes;
 }
 
 int ast_remd_loss_backward_f32(const float* x, const float* y, const float* inv_x, const float* inv_y,
@@ -630,19 +594,16 @@ int ast_remd_loss_backward_f32(const float* x, const float* y, const float* inv_
   int e = pair_shape(n, ns, m, p);
   if (!e) e = chan_shape(c);
   if (e) return e;
-  if (workspace_bytes < bwd_ws(n, m, p)) return AST_E_SHAPE;
+  const BwdWs w = bwd_ws(workspace, n, m, p);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)workspace;
-  int* start = (int*)w;
-  int* cursor = (int*)(w + start_bytes(n, m));
-  int* list = (int*)(w + start_bytes(n, m) + cursor_bytes(n, m));
-  hipLaunchKernelGGL(remd_invert_kernel, dim3(n), dim3(kT), 0, st, col_index, branch, start, cursor, list, m, p);
+  hipLaunchKernelGGL(remd_invert_kernel, dim3(n), dim3(kT), 0, st, col_index, branch, w.start, w.cursor, w.list, m, p);
   const dim3 grid((m + kT - 1) / kT, (c + GC - 1) / GC, n);
   hipLaunchKernelGGL(remd_bwd_row_kernel, grid, dim3(kT), 0, st, x, y, inv_x, inv_y, row_min, row_index, branch,
                      grad_scale, dx, c, m, p, ns, weight / ((float)n * (float)m));
   const dim3 cgrid((m + kT - 1) / kT, (c + GCC - 1) / GCC, n);
-  hipLaunchKernelGGL(remd_bwd_col_kernel, cgrid, dim3(kT), 0, st, x, y, inv_x, inv_y, col_min, (const int*)start,
-                     (const int*)list, branch, grad_scale, dx, c, m, p, ns, weight / ((float)n * (float)p));
+  hipLaunchKernelGGL(remd_bwd_col_kernel, cgrid, dim3(kT), 0, st, x, y, inv_x, inv_y, col_min, (const int*)w.start,
+                     (const int*)w.list, branch, grad_scale, dx, c, m, p, ns, weight / ((float)n * (float)p));
   return (int)hipGetLastError();
 }
 

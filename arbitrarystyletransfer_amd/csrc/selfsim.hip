@@ -35,13 +35,19 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "match_tile.h"
 #include "wave.h"
+#include "ws.h"
 
 namespace {
 
+using ast_tile::acc_row;
+using ast_tile::f32x16;
+using ast_tile::quarter_sum;
+using ast_tile::stage_load;
+using ast_tile::stage_store;
 using ast_wave::block_sum;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kT = 256;     // threads per workgroup everywhere in this file
 constexpr int MT = 64;      // pixels per tile side (4 waves x 32 x 32)
 constexpr int KC = 64;      // channels per staged chunk of the pairs kernel
@@ -52,9 +58,6 @@ constexpr int CH = 128;     // channels per workgroup of the backward GEMM: 32 a
 constexpr int XP = MT + 1;  // padded row of the backward's x tile in LDS
 
 __device__ __forceinline__ float inv_colsum(float r) { return (r > 0.f && r < INFINITY) ? 1.0f / r : 0.f; }
-
-// the lane's accumulator row k of a 32 x 32 MFMA block: rows 4 h .. 4 h + 3, then every 8
-__device__ __forceinline__ int acc_row(int k, int h) { return (k & 3) + 8 * (k >> 2) + 4 * h; }
 
 // ------------------------------------------------------------------------------------------------
 // Column sums
@@ -97,8 +100,8 @@ __global__ __launch_bounds__(kT) void selfsim_colsum_kernel(const float* __restr
   shq[g][lane] = q;
   __syncthreads();
   if (g == 0 && p < N) {
-    const float dot = ((shd[0][lane] + shd[1][lane]) + shd[2][lane]) + shd[3][lane];
-    const float sq = ((shq[0][lane] + shq[1][lane]) + shq[2][lane]) + shq[3][lane];
+    const float dot = quarter_sum(shd, lane);
+    const float sq = quarter_sum(shq, lane);
     rsum[(int64_t)b * N + p] = (float)(N - 1) - (dot - sq);
   }
 }
@@ -107,23 +110,8 @@ __global__ __launch_bounds__(kT) void selfsim_colsum_kernel(const float* __restr
 // Pairs
 // ------------------------------------------------------------------------------------------------
 
-// As remd.hip's: the chunk whose first channel plane is `chunk` (`cleft` >= 1 channels are left from
-// there) into registers, wave w channels w, w + 4, ..., lane l pixel p0 + l. The descriptor ends with the
-// chunk's last real channel: a channel past C reads as 0, and so does anything past the sample. A pixel
-// past the map reads the next channel's first pixels; such a row or column of the tile is masked.
-__device__ __forceinline__ void stage_load(float (&reg)[RT], const float* chunk, int cleft, int hw, int p0, int wave,
-                                           int lane) {
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(chunk), 0, 4 * min(cleft, KC) * hw, 0x00020000);
-#pragma unroll
-  for (int t = 0; t < RT; ++t)
-    reg[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, 4 * ((wave + 4 * t) * hw + p0 + lane), 0, 0));
-}
-
-__device__ __forceinline__ void stage_store(const float (&reg)[RT], float* S, int wave, int lane) {
-#pragma unroll
-  for (int t = 0; t < RT; ++t) S[(wave + 4 * t) * MT + lane] = reg[t];
-}
+// stage_load / stage_store (match_tile.h): a chunk of KC channels x 64 pixels into registers, then LDS. A
+// pixel past the map reads the next channel's first pixels; such a row or column of the tile is masked.
 
 // the first pair of tile row I in the list (0, 0), (0, 1), ..., (0, T - 1), (1, 1), ...
 __device__ __host__ inline int tri_start(int I, int T) { return I * T - I * (I - 1) / 2; }
@@ -424,7 +412,7 @@ __global__ __launch_bounds__(kT) void selfsim_finish_kernel(const float* __restr
   sh[q][lane] = d;
   __syncthreads();
   if (p >= N) return;
-  const float dot = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+  const float dot = quarter_sum(sh, lane);
   const float k = -(g[0] * w_over_nn) * up;
   for (int ch = q; ch < C; ch += 4) {
     const int64_t o = base + (int64_t)ch * N;
@@ -436,26 +424,43 @@ __global__ __launch_bounds__(kT) void selfsim_finish_kernel(const float* __restr
 // Host side: argument checks, workspace layouts, launch sequences
 // ------------------------------------------------------------------------------------------------
 
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-inline int tiles_of(int pixels) { return (pixels + MT - 1) / MT; }
+using ast_tile::tiles_of;
 inline int pairs_of(int pixels) { return tiles_of(pixels) * (tiles_of(pixels) + 1) / 2; }
 
-inline int map_shape(int n, int pixels) {
-  return (n <= 0 || n > 65535 || pixels <= 0 || pixels > kMaxPixels) ? AST_E_SHAPE : AST_OK;
-}
-inline int chan_shape(int c) { return c <= 0 ? AST_E_SHAPE : c > kMaxC ? AST_E_UNSUPPORTED : AST_OK; }
+inline int map_shape(int n, int pixels) { return ast_tile::map_shape(n, pixels, kMaxPixels); }
+inline int chan_shape(int c) { return ast_tile::chan_shape(c, kMaxC); }
 inline int all_shape(int n, int c, int pixels) {
   const int e = map_shape(n, pixels);
   return e ? e : chan_shape(c);
 }
 
-inline int64_t colsum_ws(int n, int c) { return al256((int64_t)4 * n * c); }
-// [t partials | loss partials]
-inline int64_t tpart_bytes(int n, int pixels) { return al256((int64_t)4 * n * tiles_of(pixels) * pixels); }
-inline int64_t pairs_ws(int n, int pixels) { return tpart_bytes(n, pixels) + al256((int64_t)4 * n * pairs_of(pixels)); }
-// [channel sums | pairs]
-inline int64_t loss_ws(int n, int c, int pixels) { return colsum_ws(n, c) + pairs_ws(n, pixels); }
-inline int64_t bwd_ws(int n, int c, int pixels) { return al256((int64_t)4 * n * c * pixels); }
+// A workspace of one region is its size: the column sums' [channel sums] and the backward's [G]
+inline int64_t colsum_ws(int n, int c) { return ast_ws::al256((int64_t)4 * n * c); }
+inline int64_t bwd_ws(int n, int c, int pixels) { return ast_ws::al256((int64_t)4 * n * c * pixels); }
+
+// The pairs' workspace: [t partials | loss partials]
+struct PairsWs {
+  float *tpart, *lpart;
+  int64_t bytes;
+};
+
+inline PairsWs pairs_ws(void* base, int n, int pixels) {
+  ast_ws::Walk wk(base);
+  return {wk.take<float>((int64_t)4 * n * tiles_of(pixels) * pixels), wk.take<float>((int64_t)4 * n * pairs_of(pixels)),
+          wk.off};
+}
+
+// The whole loss's workspace: [the column sums' | the pairs']
+struct LossWs {
+  float* S;
+  void* pairs;
+  int64_t bytes;
+};
+
+inline LossWs loss_ws(void* base, int n, int c, int pixels) {
+  ast_ws::Walk wk(base);
+  return {wk.take<float>(colsum_ws(n, c)), wk.take<void>(pairs_ws(nullptr, n, pixels).bytes), wk.off};
+}
 
 int colsum_launch(const float* x, const float* u, float* r, int n, int c, int pixels, float* S, hipStream_t st) {
   hipLaunchKernelGGL(selfsim_chsum_kernel, dim3(c, n), dim3(kT), 0, st, x, u, S, c, pixels);
@@ -465,11 +470,11 @@ int colsum_launch(const float* x, const float* u, float* r, int n, int c, int pi
 }
 
 int pairs_launch(const float* x, const float* c, const float* ux, const float* uc, const float* rx, const float* rc,
-                 float* sums, float* t, long long* pos, long long* neg, int n, int ch, int pixels, unsigned char* wsp,
+                 float* sums, float* t, long long* pos, long long* neg, int n, int ch, int pixels, void* wsp,
                  hipStream_t st) {
   const int T = tiles_of(pixels), pairs = pairs_of(pixels);
-  float* tpart = (float*)wsp;
-  float* lpart = (float*)(wsp + tpart_bytes(n, pixels));
+  const PairsWs w = pairs_ws(wsp, n, pixels);
+  float *tpart = w.tpart, *lpart = w.lpart;
   hipLaunchKernelGGL(selfsim_pairs_kernel, dim3(pairs, n), dim3(kT), 0, st, x, c, ux, uc, rx, rc, lpart, tpart,
                      (uint32_t*)pos, (uint32_t*)neg, ch, pixels, T);
   hipLaunchKernelGGL(selfsim_tmerge_kernel, dim3((pixels + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)tpart, rx, t,
@@ -504,7 +509,7 @@ int ast_selfsim_colsum_f32(const float* x, const float* inv_norm, float* col_sum
 
 long long ast_selfsim_pairs_workspace_bytes(int n, int pixels) {
   const int e = map_shape(n, pixels);
-  return e ? e : pairs_ws(n, pixels);
+  return e ? e : pairs_ws(nullptr, n, pixels).bytes;
 }
 
 int ast_selfsim_pairs_f32(const float* x, const float* c, const float* inv_x, const float* inv_c, const float* r_x,
@@ -513,9 +518,8 @@ int ast_selfsim_pairs_f32(const float* x, const float* c, const float* inv_x, co
   if (!x || !c || !inv_x || !inv_c || !r_x || !r_c || !sums || !t || !pos || !neg || !workspace) return AST_E_NULLPTR;
   const int e = all_shape(n, ch, pixels);
   if (e) return e;
-  if (workspace_bytes < pairs_ws(n, pixels)) return AST_E_SHAPE;
-  return pairs_launch(x, c, inv_x, inv_c, r_x, r_c, sums, t, pos, neg, n, ch, pixels, (unsigned char*)workspace,
-                      (hipStream_t)stream);
+  if (workspace_bytes < pairs_ws(nullptr, n, pixels).bytes) return AST_E_SHAPE;
+  return pairs_launch(x, c, inv_x, inv_c, r_x, r_c, sums, t, pos, neg, n, ch, pixels, workspace, (hipStream_t)stream);
 }
 
 int ast_selfsim_total_f32(const float* sums, float* loss, int n, float weight, void* stream) {
@@ -526,7 +530,7 @@ int ast_selfsim_total_f32(const float* sums, float* loss, int n, float weight, v
 
 long long ast_selfsim_loss_workspace_bytes(int n, int c, int pixels) {
   const int e = all_shape(n, c, pixels);
-  return e ? e : loss_ws(n, c, pixels);
+  return e ? e : loss_ws(nullptr, n, c, pixels).bytes;
 }
 
 int ast_selfsim_loss_f32(const float* x, const float* c, float* inv_x, float* inv_c, float* r_x, float* r_c, float* t,
@@ -536,18 +540,18 @@ int ast_selfsim_loss_f32(const float* x, const float* c, float* inv_x, float* in
     return AST_E_NULLPTR;
   int e = all_shape(n, ch, pixels);
   if (e) return e;
-  if (workspace_bytes < loss_ws(n, ch, pixels)) return AST_E_SHAPE;
+  const LossWs w = loss_ws(workspace, n, ch, pixels);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)workspace;
   e = ast_cosine_norms_f32(x, inv_x, n, ch, pixels, stream);
   if (e) return e;
   e = ast_cosine_norms_f32(c, inv_c, n, ch, pixels, stream);
   if (e) return e;
-  e = colsum_launch(x, inv_x, r_x, n, ch, pixels, (float*)w, st);
+  e = colsum_launch(x, inv_x, r_x, n, ch, pixels, w.S, st);
   if (e) return e;
-  e = colsum_launch(c, inv_c, r_c, n, ch, pixels, (float*)w, st);
+  e = colsum_launch(c, inv_c, r_c, n, ch, pixels, w.S, st);
   if (e) return e;
-  e = pairs_launch(x, c, inv_x, inv_c, r_x, r_c, sums, t, pos, neg, n, ch, pixels, w + colsum_ws(n, ch), st);
+  e = pairs_launch(x, c, inv_x, inv_c, r_x, r_c, sums, t, pos, neg, n, ch, pixels, w.pairs, st);
   if (e) return e;
   return total_launch(sums, loss, n, weight, st);
 }

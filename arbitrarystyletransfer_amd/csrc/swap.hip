@@ -47,17 +47,21 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "match_tile.h"
+#include "ws.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ast_tile::acc_row;
+using ast_tile::f32x16;
+using ast_tile::fold_arg;
+
 constexpr int kT = 256;            // threads per workgroup everywhere in this file
 constexpr int MT = 64;             // patches per tile side (4 waves x 32 x 32)
 constexpr int KC = 8;              // channels per staged chunk: K = 72 per chunk
 constexpr int ROWS = KC * 3;       // staged runs per chunk and side: (channel, patch row)
 constexpr int RT = ROWS / 4;       // runs per wave
 constexpr int kMaxC = 1024;
-constexpr int kMaxSplits = 64;
 constexpr int kMaxPlane = 1 << 24; // pixels per map
 constexpr int kTargetWGs = 16 * 256;
 constexpr int GC = 32;             // channels per workgroup of the gather
@@ -77,14 +81,10 @@ __global__ __launch_bounds__(kT) void swap_sqnorm_kernel(const float* __restrict
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6, p = blockIdx.x * 64 + lane;
   const float* X = x + (int64_t)blockIdx.y * C * hw;
   float s = 0.f;
-  if (p < hw)
-    for (int c = g; c < C; c += 4) {
-      const float v = X[(int64_t)c * hw + p];
-      s = fmaf(v, v, s);
-    }
+  if (p < hw) s = ast_tile::quarter_sqsum(X, C, hw, g, p);
   sh[g][lane] = s;
   __syncthreads();
-  if (g == 0 && p < hw) pix[(int64_t)blockIdx.y * hw + p] = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+  if (g == 0 && p < hw) pix[(int64_t)blockIdx.y * hw + p] = ast_tile::quarter_sum(sh, lane);
 }
 
 // grid (patches / 256, samples): inv[b, j] = 1 / sqrt(box sum), 0 unless the sum is positive.
@@ -147,14 +147,6 @@ __device__ __forceinline__ void stage_store(const float (&reg)[RT][NP], float* S
   for (int ps = 0; ps < NP; ++ps)
 #pragma unroll
     for (int t = 0; t < RT; ++t) S[(wave + 4 * t) * (64 * NP) + lane + 64 * ps] = reg[t][ps];
-}
-
-// b wins over a: greater, or equal with the lower index
-__device__ __forceinline__ void fold(float& v, int& ix, float ov, int oi) {
-  if (ov > v || (ov == v && oi < ix)) {
-    v = ov;
-    ix = oi;
-  }
 }
 
 // What the guided match reads beside the unguided one's inputs: one class
@@ -355,7 +347,7 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
     for (int o = 16; o > 0; o >>= 1) {
       const float ov = __shfl_xor(v, o, 64);
       const int oi = __shfl_xor(ix, o, 64);
-      fold(v, ix, ov, oi);
+      fold_arg<true>(v, ix, ov, oi);
     }
     best[i] = v;
     bidx[i] = ix;
@@ -363,7 +355,7 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
   if (wn == 1 && r == 0) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int row = acc_row(i, h);
       redv[wm * 32 + row] = best[i];
       redi[wm * 32 + row] = bidx[i];
     }
@@ -373,11 +365,11 @@ __global__ __launch_bounds__(kT) void swap_match_kernel(const float* __restrict_
     const int64_t ob = ((int64_t)b * gridDim.y + split) * M;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = (i & 3) + 8 * (i >> 2) + 4 * h, gi = m0 + wm * 32 + row;
+      const int row = acc_row(i, h), gi = m0 + wm * 32 + row;
       if (gi >= M) continue;
       float v = best[i];
       int ix = bidx[i];
-      fold(v, ix, redv[wm * 32 + row], redi[wm * 32 + row]);
+      fold_arg<true>(v, ix, redv[wm * 32 + row], redi[wm * 32 + row]);
       oscore[ob + gi] = v;
       oindex[ob + gi] = ix;
     }
@@ -407,20 +399,7 @@ template <int NONE>
 __global__ __launch_bounds__(kT) void swap_merge_kernel(const float* __restrict__ pscore, const int* __restrict__ pindex,
                                                        float* __restrict__ score, int* __restrict__ index, int M,
                                                        int splits) {
-  const int i = blockIdx.x * kT + threadIdx.x, b = blockIdx.y;
-  if (i >= M) return;
-  float v = -INFINITY;
-  int ix = NONE;
-  for (int s = 0; s < splits; ++s) {
-    const int64_t o = ((int64_t)b * splits + s) * M + i;
-    const float ov = pscore[o];
-    if (ov > v) {
-      v = ov;
-      ix = pindex[o];
-    }
-  }
-  score[(int64_t)b * M + i] = v;
-  index[(int64_t)b * M + i] = ix;
+  ast_tile::merge_slots<true, kT>(pscore, pindex, score, index, M, splits, NONE);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -515,9 +494,8 @@ __global__ __launch_bounds__(kT) void swap_gather_guided_kernel(const float* __r
 // Host side: argument checks, workspace layouts, launch sequences
 // ------------------------------------------------------------------------------------------------
 
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+using ast_tile::tiles_of;
 inline int64_t patches(int h, int w) { return (int64_t)(h - 2) * (w - 2); }
-inline int tiles_of(int64_t p) { return (int)((p + MT - 1) / MT); }
 
 // AST_OK, or the code that rejects a map of `n` samples and sides h x w
 inline int map_shape(int n, int h, int w) {
@@ -531,32 +509,53 @@ inline int pair_shape(int n, int ns, int hc, int wc, int hs, int ws) {
   return e ? e : map_shape(ns, hs, ws);
 }
 
-inline int chan_shape(int c) { return c <= 0 ? AST_E_SHAPE : c > kMaxC ? AST_E_UNSUPPORTED : AST_OK; }
+inline int chan_shape(int c) { return ast_tile::chan_shape(c, kMaxC); }
 
-// Splits of the style tiles: as asked (clamped to the tiles), or, for 0, as many as bring the grid to
-// kTargetWGs workgroups -- about 16 per CU: three are resident per CU and short ones even out the tail
-// (measured at C = 512, 64 x 64: 61 splits at n = 1, 9 at n = 8) --; then rounded so that no split is empty.
-inline int split_tiles(int64_t wgs, int ntiles, int want, int* tiles_per_split) {
-  int64_t s = want > 0 ? want : (kTargetWGs + wgs - 1) / wgs;
-  if (s > kMaxSplits) s = kMaxSplits;
-  if (s > ntiles) s = ntiles;
-  if (s < 1) s = 1;
-  const int tps = (int)((ntiles + s - 1) / s);
-  if (tiles_per_split) *tiles_per_split = tps;
-  return (ntiles + tps - 1) / tps;
+// A workspace of one region is its size: the norms' [squared pixel norms]
+inline int64_t norms_ws(int ns, int hs, int ws) { return ast_ws::al256((int64_t)4 * ns * hs * ws); }
+
+// The match's workspace: [score scratch | content tile masks | bank tile masks | partial scores |
+// partial indices]; the masks only for the guided match (S > 0 styles in the bank), the partials only
+// when there is more than one split. Splits of the style tiles (ast_tile::split_tiles), of the bank
+// tiles when guided, whatever the classes are (the count must not depend on device data; under
+// skipping the runs do unequal work, which the many workgroups per CU even out): as asked (clamped to
+// the tiles), or, for 0, as many as bring the grid to kTargetWGs workgroups -- about 16 per CU: three
+// are resident per CU and short ones even out the tail (measured at C = 512, 64 x 64: 61 splits at
+// n = 1, 9 at n = 8).
+struct MatchWs {
+  int splits, tiles_per_split;
+  float* score;
+  unsigned long long *cmask, *bmask;
+  float* pscore;
+  int* pindex;
+  int64_t bytes;
+};
+
+inline MatchWs match_ws(void* base, int n, int S, int hc, int wc, int hs, int ws, int want) {
+  ast_ws::Walk wk(base);
+  const int64_t m = patches(hc, wc);
+  const int ct = tiles_of(m), bt = (S > 0 ? S : 1) * tiles_of(patches(hs, ws));
+  int tps = 0;
+  const int s = ast_tile::split_tiles((int64_t)n * ct, bt, want, kTargetWGs, 1, &tps);
+  using u64 = unsigned long long;
+  return {s, tps, wk.take<float>(4 * n * m), S > 0 ? wk.take<u64>((int64_t)8 * n * ct) : nullptr,
+          S > 0 ? wk.take<u64>((int64_t)8 * bt) : nullptr, s > 1 ? wk.take<float>(4 * n * s * m) : nullptr,
+          s > 1 ? wk.take<int>(4 * n * s * m) : nullptr, wk.off};
 }
 
-inline int match_splits(int n, int hc, int wc, int hs, int ws, int want, int* tiles_per_split) {
-  return split_tiles((int64_t)n * tiles_of(patches(hc, wc)), tiles_of(patches(hs, ws)), want, tiles_per_split);
-}
+// The whole op's workspace: [inverse norms | index | scratch], the scratch the norms' workspace, then
+// the match's (the guided match's for a bank of S > 0 styles): stream order keeps them apart
+struct SwapWs {
+  float* inv;
+  int* index;
+  void* scratch;
+  int64_t bytes;
+};
 
-inline int64_t norms_ws(int ns, int hs, int ws) { return al256((int64_t)4 * ns * hs * ws); }
-
-// [score scratch | partial scores | partial indices]
-inline int64_t match_ws(int n, int hc, int wc, int hs, int ws, int want) {
-  const int s = match_splits(n, hc, wc, hs, ws, want, nullptr);
-  const int64_t one = al256((int64_t)4 * n * patches(hc, wc));
-  return one + (s > 1 ? 2 * al256((int64_t)4 * n * s * patches(hc, wc)) : 0);
+inline SwapWs swap_ws(void* base, int n, int ns, int S, int hc, int wc, int hs, int ws) {
+  ast_ws::Walk wk(base);
+  return {wk.take<float>(4 * ns * patches(hs, ws)), wk.take<int>(4 * n * patches(hc, wc)),
+          wk.take<void>(std::max<int64_t>(norms_ws(ns, hs, ws), match_ws(nullptr, n, S, hc, wc, hs, ws, 0).bytes)), wk.off};
 }
 
 int norms_launch(const float* sk, float* inv, int ns, int c, int hs, int ws, float* pix, hipStream_t st) {
@@ -568,20 +567,19 @@ int norms_launch(const float* sk, float* inv, int ns, int c, int hs, int ws, flo
 }
 
 int match_launch(const float* ck, const float* sk, const float* inv, int* index, float* score, int n, int ns, int c,
-                 int hc, int wc, int hs, int ws, int want, unsigned char* wsp, hipStream_t st) {
-  int tps = 0;
-  const int splits = match_splits(n, hc, wc, hs, ws, want, &tps);
+                 int hc, int wc, int hs, int ws, int want, void* wsp, hipStream_t st) {
+  const MatchWs w = match_ws(wsp, n, 0, hc, wc, hs, ws, want);
+  const int splits = w.splits, tps = w.tiles_per_split;
   const int m = (int)patches(hc, wc);
-  const int64_t one = al256((int64_t)4 * n * m);
-  if (!score) score = (float*)wsp;
+  if (!score) score = w.score;
   const dim3 grid(tiles_of(m), splits, n);
   // a tile's run is 63 patches + 2 pixels per image row crossed + 3: within 128 when a row has 3 patches or more
   auto kern = (wc >= 5 && ws >= 5) ? swap_match_kernel<2> : swap_match_kernel<3>;
   if (splits == 1) {
     hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, score, index, c, hc, wc, hs, ws, ns, tps);
   } else {
-    float* ps = (float*)(wsp + one);
-    int* pi = (int*)(wsp + one + al256((int64_t)4 * n * splits * m));
+    float* ps = w.pscore;
+    int* pi = w.pindex;
     hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, ps, pi, c, hc, wc, hs, ws, ns, tps);
     hipLaunchKernelGGL(swap_merge_kernel<0>, dim3((m + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)ps, (const int*)pi,
                        score, index, m, splits);
@@ -607,36 +605,14 @@ inline int bank_shape(int n, int S, int hc, int wc, int hs, int ws) {
   return e;
 }
 
-inline int bank_tiles(int S, int hs, int ws) { return S * tiles_of(patches(hs, ws)); }
-
-// Splits of the bank tiles, chosen as the unguided match chooses them: equal runs of bank tiles,
-// whatever the classes are (the count must not depend on device data). Under skipping the runs do
-// unequal work; the grid is many workgroups per CU, which evens that out.
-inline int guided_splits(int n, int S, int hc, int wc, int hs, int ws, int want, int* tiles_per_split) {
-  return split_tiles((int64_t)n * tiles_of(patches(hc, wc)), bank_tiles(S, hs, ws), want, tiles_per_split);
-}
-
-inline int64_t cmask_bytes(int n, int hc, int wc) { return al256((int64_t)8 * n * tiles_of(patches(hc, wc))); }
-
-// [score scratch | content tile masks | bank tile masks | partial scores | partial indices]
-inline int64_t guided_match_ws(int n, int S, int hc, int wc, int hs, int ws, int want) {
-  const int s = guided_splits(n, S, hc, wc, hs, ws, want, nullptr);
-  const int64_t one = al256((int64_t)4 * n * patches(hc, wc));
-  return one + cmask_bytes(n, hc, wc) + al256((int64_t)8 * bank_tiles(S, hs, ws)) +
-         (s > 1 ? 2 * al256((int64_t)4 * n * s * patches(hc, wc)) : 0);
-}
-
 int guided_match_launch(const float* ck, const float* sk, const float* inv, const uint8_t* cc, const uint8_t* sc,
                         int* index, float* score, int n, int S, int c, int hc, int wc, int hs, int ws, int want,
-                        int flags, unsigned char* wsp, hipStream_t st) {
-  int tps = 0;
-  const int splits = guided_splits(n, S, hc, wc, hs, ws, want, &tps);
+                        int flags, void* wsp, hipStream_t st) {
+  const MatchWs w = match_ws(wsp, n, S, hc, wc, hs, ws, want);
+  const int splits = w.splits, tps = w.tiles_per_split;
   const int m = (int)patches(hc, wc), ns = (int)patches(hs, ws), ct = tiles_of(m), bt = tiles_of(ns);
-  const int64_t one = al256((int64_t)4 * n * m);
-  if (!score) score = (float*)wsp;
-  unsigned long long* cmask = (unsigned long long*)(wsp + one);
-  unsigned long long* bmask = (unsigned long long*)(wsp + one + cmask_bytes(n, hc, wc));
-  unsigned char* part = (unsigned char*)bmask + al256((int64_t)8 * S * bt);
+  if (!score) score = w.score;
+  unsigned long long *cmask = w.cmask, *bmask = w.bmask;
   hipLaunchKernelGGL(swap_class_mask_kernel, dim3(ct, n), dim3(64), 0, st, cc, cmask, m);
   hipLaunchKernelGGL(swap_class_mask_kernel, dim3(bt, S), dim3(64), 0, st, sc, bmask, ns);
   const Guide g{cc, sc, cmask, bmask, flags};
@@ -645,8 +621,8 @@ int guided_match_launch(const float* ck, const float* sk, const float* inv, cons
   if (splits == 1) {
     hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, score, index, c, hc, wc, hs, ws, S, tps, g);
   } else {
-    float* ps = (float*)part;
-    int* pi = (int*)(part + al256((int64_t)4 * n * splits * m));
+    float* ps = w.pscore;
+    int* pi = w.pindex;
     hipLaunchKernelGGL(kern, grid, dim3(kT), 0, st, ck, sk, inv, ps, pi, c, hc, wc, hs, ws, S, tps, g);
     hipLaunchKernelGGL(swap_merge_kernel<-1>, dim3((m + kT - 1) / kT, n), dim3(kT), 0, st, (const float*)ps,
                        (const int*)pi, score, index, m, splits);
@@ -684,7 +660,7 @@ long long ast_patch_match_workspace_bytes(int n, int ns, int hc, int wc, int hs,
   const int e = pair_shape(n, ns, hc, wc, hs, ws);
   if (e) return e;
   if (splits < 0) return AST_E_UNSUPPORTED;
-  return match_ws(n, hc, wc, hs, ws, splits);
+  return match_ws(nullptr, n, 0, hc, wc, hs, ws, splits).bytes;
 }
 
 int ast_patch_match_ex_f32(const float* content_key, const float* style_key, const float* inv_norm, int* index,
@@ -695,9 +671,9 @@ int ast_patch_match_ex_f32(const float* content_key, const float* style_key, con
   if (!e) e = chan_shape(c);
   if (e) return e;
   if (splits < 0) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < match_ws(n, hc, wc, hs, ws, splits)) return AST_E_SHAPE;
-  return match_launch(content_key, style_key, inv_norm, index, score_or_null, n, ns, c, hc, wc, hs, ws, splits,
-                      (unsigned char*)workspace, (hipStream_t)stream);
+  if (workspace_bytes < match_ws(nullptr, n, 0, hc, wc, hs, ws, splits).bytes) return AST_E_SHAPE;
+  return match_launch(content_key, style_key, inv_norm, index, score_or_null, n, ns, c, hc, wc, hs, ws, splits, workspace,
+                      (hipStream_t)stream);
 }
 
 int ast_patch_match_f32(const float* content_key, const float* style_key, const float* inv_norm, int* index,
@@ -716,12 +692,9 @@ int ast_patch_gather_f32(const float* style_value, const int* index, const float
   return gather_launch(style_value, index, content, out, n, ns, c, hc, wc, hs, ws, (float)alpha, (hipStream_t)stream);
 }
 
-// [inverse norms | index | the larger of the norms' and the match's scratch]
 long long ast_style_swap_workspace_bytes(int n, int ns, int hc, int wc, int hs, int ws) {
   const int e = pair_shape(n, ns, hc, wc, hs, ws);
-  if (e) return e;
-  const int64_t a = norms_ws(ns, hs, ws), b = match_ws(n, hc, wc, hs, ws, 0);
-  return al256((int64_t)4 * ns * patches(hs, ws)) + al256((int64_t)4 * n * patches(hc, wc)) + (a > b ? a : b);
+  return e ? e : swap_ws(nullptr, n, ns, 0, hc, wc, hs, ws).bytes;
 }
 
 int ast_style_swap_f32(const float* content_key, const float* style_key, const float* style_value, const float* content,
@@ -731,16 +704,13 @@ int ast_style_swap_f32(const float* content_key, const float* style_key, const f
   int e = pair_shape(n, ns, hc, wc, hs, ws);
   if (!e) e = chan_shape(c);
   if (e) return e;
-  if (workspace_bytes < ast_style_swap_workspace_bytes(n, ns, hc, wc, hs, ws)) return AST_E_SHAPE;
+  const SwapWs w = swap_ws(workspace, n, ns, 0, hc, wc, hs, ws);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)workspace;
-  float* inv = (float*)w;
-  int* index = (int*)(w + al256((int64_t)4 * ns * patches(hs, ws)));
-  unsigned char* scratch = (unsigned char*)index + al256((int64_t)4 * n * patches(hc, wc));
-  if (index_or_null) index = index_or_null;
-  e = norms_launch(style_key, inv, ns, c, hs, ws, (float*)scratch, st);
+  int* index = index_or_null ? index_or_null : w.index;
+  e = norms_launch(style_key, w.inv, ns, c, hs, ws, (float*)w.scratch, st);
   if (e) return e;
-  e = match_launch(content_key, style_key, inv, index, score_or_null, n, ns, c, hc, wc, hs, ws, 0, scratch, st);
+  e = match_launch(content_key, style_key, w.inv, index, score_or_null, n, ns, c, hc, wc, hs, ws, 0, w.scratch, st);
   if (e) return e;
   return gather_launch(style_value, index, content, out, n, ns, c, hc, wc, hs, ws, (float)alpha, st);
 }
@@ -751,7 +721,7 @@ long long ast_patch_match_guided_workspace_bytes(int n, int s, int hc, int wc, i
   const int e = bank_shape(n, s, hc, wc, hs, ws);
   if (e) return e;
   if (splits < 0) return AST_E_UNSUPPORTED;
-  return guided_match_ws(n, s, hc, wc, hs, ws, splits);
+  return match_ws(nullptr, n, s, hc, wc, hs, ws, splits).bytes;
 }
 
 int ast_patch_match_guided_ex_f32(const float* content_key, const float* style_keys, const float* inv_norm,
@@ -764,9 +734,9 @@ int ast_patch_match_guided_ex_f32(const float* content_key, const float* style_k
   if (!e) e = chan_shape(c);
   if (e) return e;
   if (splits < 0 || (flags & ~AST_SWAP_NO_SKIP)) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < guided_match_ws(n, s, hc, wc, hs, ws, splits)) return AST_E_SHAPE;
+  if (workspace_bytes < match_ws(nullptr, n, s, hc, wc, hs, ws, splits).bytes) return AST_E_SHAPE;
   return guided_match_launch(content_key, style_keys, inv_norm, content_class, style_class, index, score_or_null, n, s,
-                             c, hc, wc, hs, ws, splits, flags, (unsigned char*)workspace, (hipStream_t)stream);
+                             c, hc, wc, hs, ws, splits, flags, workspace, (hipStream_t)stream);
 }
 
 int ast_patch_gather_guided_f32(const float* style_values, const int* index, const float* content, float* out, int n,
@@ -779,12 +749,9 @@ int ast_patch_gather_guided_f32(const float* style_values, const int* index, con
                               (hipStream_t)stream);
 }
 
-// [inverse norms | index | the larger of the norms' and the guided match's scratch]
 long long ast_style_swap_guided_workspace_bytes(int n, int s, int hc, int wc, int hs, int ws) {
   const int e = bank_shape(n, s, hc, wc, hs, ws);
-  if (e) return e;
-  const int64_t a = norms_ws(s, hs, ws), b = guided_match_ws(n, s, hc, wc, hs, ws, 0);
-  return al256((int64_t)4 * s * patches(hs, ws)) + al256((int64_t)4 * n * patches(hc, wc)) + (a > b ? a : b);
+  return e ? e : swap_ws(nullptr, n, s, s, hc, wc, hs, ws).bytes;
 }
 
 int ast_style_swap_guided_f32(const float* content_key, const float* style_keys, const float* style_values,
@@ -797,17 +764,14 @@ int ast_style_swap_guided_f32(const float* content_key, const float* style_keys,
   int e = bank_shape(n, s, hc, wc, hs, ws);
   if (!e) e = chan_shape(c);
   if (e) return e;
-  if (workspace_bytes < ast_style_swap_guided_workspace_bytes(n, s, hc, wc, hs, ws)) return AST_E_SHAPE;
+  const SwapWs w = swap_ws(workspace, n, s, s, hc, wc, hs, ws);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)workspace;
-  float* inv = (float*)w;
-  int* index = (int*)(w + al256((int64_t)4 * s * patches(hs, ws)));
-  unsigned char* scratch = (unsigned char*)index + al256((int64_t)4 * n * patches(hc, wc));
-  if (index_or_null) index = index_or_null;
-  e = norms_launch(style_keys, inv, s, c, hs, ws, (float*)scratch, st);
+  int* index = index_or_null ? index_or_null : w.index;
+  e = norms_launch(style_keys, w.inv, s, c, hs, ws, (float*)w.scratch, st);
   if (e) return e;
-  e = guided_match_launch(content_key, style_keys, inv, content_class, style_class, index, score_or_null, n, s, c, hc,
-                          wc, hs, ws, 0, 0, scratch, st);
+  e = guided_match_launch(content_key, style_keys, w.inv, content_class, style_class, index, score_or_null, n, s, c, hc,
+                          wc, hs, ws, 0, 0, w.scratch, st);
   if (e) return e;
   return guided_gather_launch(style_values, index, content, out, n, s, c, hc, wc, hs, ws, (float)alpha, st);
 }

@@ -21,11 +21,13 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ast_hip.h"
+#include "match_tile.h"
 #include "wave.h"
+#include "ws.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using ast_tile::f32x16;
 constexpr int kT = 256;                 // threads per workgroup everywhere in this file
 constexpr int WT = 64, WK = 32, WP = WT + 1, WL = WK * WT / kT;
 constexpr int kMaxC = 1024;
@@ -589,9 +591,9 @@ __global__ __launch_bounds__(kT) void wct_region_apply_kernel(const float* __res
 // Host side: argument checks, workspace layouts, launch sequences
 // ------------------------------------------------------------------------------------------------
 
-inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+using ast_ws::al256;
+using ast_tile::tiles_of;  // WT = 64
 inline bool eps_ok(float e) { return e >= 1e-4f && e <= 1.f; }
-inline int tiles_of(int c) { return (c + WT - 1) / WT; }
 
 inline int default_iters(int c, float eps_rel) {
   return (int)ceil(log((double)c / (double)eps_rel) / log(2.25)) + 5;
@@ -604,13 +606,26 @@ inline int cov_shape(int n, int c, int64_t m) {
   return AST_OK;
 }
 
-inline int64_t cov_ws(int n, int c, int64_t m) {
+// A workspace of one region is its size. Covariance partials, of the plain and of the regional stage:
+// [slots x tile pairs x 64 x 64 per matrix]; the apply stage's: [T]
+inline int64_t part_ws(int matrices, int c, int slots) {
   const int t = tiles_of(c);
-  return al256((int64_t)4 * n * cov_splits(m, nullptr) * (t * (t + 1) / 2) * (WT * WT));
+  return al256((int64_t)4 * matrices * slots * (t * (t + 1) / 2) * (WT * WT));
 }
-
-inline int64_t sqrt_ws(int b, int c) { return al256((int64_t)4 * b) + 5 * al256((int64_t)4 * b * c * c); }
+inline int64_t cov_ws(int n, int c, int64_t m) { return part_ws(n, c, cov_splits(m, nullptr)); }
 inline int64_t apply_ws(int n, int c) { return al256((int64_t)4 * n * c * c); }
+
+// The Newton-Schulz iteration's workspace: [norm | Y, Z | Y, Z | P], the pairs ping-pong
+struct SqrtWs {
+  float *norm, *yz[2], *P;
+  int64_t bytes;
+};
+
+inline SqrtWs sqrt_ws(void* base, int b, int c) {
+  ast_ws::Walk wk(base);
+  const int64_t mb = al256((int64_t)4 * b * c * c);  // one matrix per sample
+  return {wk.take<float>((int64_t)4 * b), {wk.take<float>(2 * mb), wk.take<float>(2 * mb)}, wk.take<float>(mb), wk.off};
+}
 
 int cov_launch(const float* x, float* mean, float* cov, int n, int c, int64_t m, float eps_rel, float* part,
                hipStream_t st) {
@@ -624,12 +639,10 @@ int cov_launch(const float* x, float* mean, float* cov, int n, int c, int64_t m,
   return (int)hipGetLastError();
 }
 
-int sqrt_launch(const float* cov, float* root, float* iroot, int b, int c, int iters, unsigned char* ws,
+int sqrt_launch(const float* cov, float* root, float* iroot, int b, int c, int iters, void* wsp,
                 hipStream_t st) {
-  const int64_t mb = al256((int64_t)4 * b * c * c);
-  float* norm = (float*)ws;
-  float* yz[2] = {(float*)(ws + al256((int64_t)4 * b)), (float*)(ws + al256((int64_t)4 * b) + 2 * mb)};
-  float* P = (float*)(ws + al256((int64_t)4 * b) + 4 * mb);
+  const SqrtWs ws = sqrt_ws(wsp, b, c);
+  float *norm = ws.norm, *const *yz = ws.yz, *P = ws.P;
   const int64_t cc = (int64_t)c * c;
   const int t = tiles_of(c);
   const dim3 eg((unsigned)((cc + kT - 1) / kT), b);
@@ -667,7 +680,31 @@ int pair_shape(int n, int ns, int c, int64_t mc, int64_t ms) {
   return n + ns > 32767 ? AST_E_SHAPE : AST_OK;
 }
 
-inline int64_t max3(int64_t a, int64_t b, int64_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+// The matrices of a compound op: [mean | cov | sqrt | isqrt], b of each
+struct MatWs {
+  float *mean, *cov, *root, *iroot;
+};
+
+inline MatWs mat_ws(ast_ws::Walk& wk, int b, int c) {
+  const int64_t mat = (int64_t)4 * b * c * c;
+  return {wk.take<float>((int64_t)4 * b * c), wk.take<float>(mat), wk.take<float>(mat), wk.take<float>(mat)};
+}
+
+// The whole op's workspace: [mean | cov | sqrt | isqrt | scratch], content samples first, then the
+// style's; the scratch is the covariance partials, then the iteration's buffers, then T, each laid
+// out by its stage: stream order keeps them apart
+struct WctWs {
+  MatWs mat;
+  void* scratch;
+  int64_t bytes;
+};
+
+inline WctWs wct_ws(void* base, int n, int ns, int c, int64_t mc, int64_t ms) {
+  ast_ws::Walk wk(base);
+  return {mat_ws(wk, n + ns, c),
+          wk.take<void>(std::max({cov_ws(n, c, mc), cov_ws(ns, c, ms), sqrt_ws(nullptr, n + ns, c).bytes, apply_ws(n, c)})),
+          wk.off};
+}
 
 // ---- regional WCT ----
 
@@ -679,24 +716,49 @@ inline int region_shape(int n, int c, int h, int w, int regions) {
   return c > kMaxC ? AST_E_UNSUPPORTED : AST_OK;
 }
 
-inline int64_t perm_ws(int n, int64_t m) { return al256((int64_t)4 * n * m); }
 // The most splits that a region of a plane of m pixels can take: max of cov_splits(mk) over mk <= m.
 // cov_splits is ceil(mk / 64) up to 448 pixels and kMaxSplits from 449 to 512, but dips below that
 // beyond (6 at 513: chunks of 96), so cov_splits(m) itself is no bound.
 inline int region_slots(int64_t m) { return m >= 64 * (kMaxSplits - 1) + 1 ? kMaxSplits : cov_splits(m, nullptr); }
 
-inline int64_t region_part_ws(int n, int c, int64_t m, int k) {
-  const int t = tiles_of(c);
-  return al256((int64_t)4 * n * k * region_slots(m) * (t * (t + 1) / 2) * (WT * WT));
-}
-inline int64_t region_cov_ws(int n, int c, int64_t m, int k) { return perm_ws(n, m) + region_part_ws(n, c, m, k); }
+inline int64_t region_part_ws(int n, int c, int64_t m, int k) { return part_ws(n * k, c, region_slots(m)); }
 
-// [valid | mmix | cmix | T] of the apply stage, after the permutation and the counts
-inline int64_t region_mix_ws(int n, int c, int k) {
-  return al256((int64_t)4 * n * k) + al256((int64_t)4 * n * k * c) + 2 * al256((int64_t)4 * n * k * c * c);
+// The regional covariance stage's workspace: [permutation | partials]
+struct RegionCovWs {
+  int* perm;
+  float* part;
+  int64_t bytes;
+};
+
+inline RegionCovWs region_cov_ws(void* base, int n, int c, int64_t m, int k) {
+  ast_ws::Walk wk(base);
+  return {wk.take<int>((int64_t)4 * n * m), wk.take<float>(region_part_ws(n, c, m, k)), wk.off};
 }
-inline int64_t region_apply_ws(int n, int c, int64_t m, int k) {
-  return perm_ws(n, m) + al256((int64_t)4 * n * k) + region_mix_ws(n, c, k);
+
+// The mixing and apply launches' workspace: [valid | mmix | cmix | T]
+struct RegionMixWs {
+  int* valid;
+  float *mmix, *cmix, *T;
+  int64_t bytes;
+};
+
+inline RegionMixWs region_mix_ws(void* base, int n, int c, int k) {
+  ast_ws::Walk wk(base);
+  const int64_t nk = (int64_t)4 * n * k;
+  return {wk.take<int>(nk), wk.take<float>(nk * c), wk.take<float>(nk * c * c), wk.take<float>(nk * c * c), wk.off};
+}
+
+// The regional apply stage's workspace: [permutation | counts | the mixing and apply launches']
+struct RegionApplyWs {
+  int *perm, *count;
+  void* mix;
+  int64_t bytes;
+};
+
+inline RegionApplyWs region_apply_ws(void* base, int n, int c, int64_t m, int k) {
+  ast_ws::Walk wk(base);
+  return {wk.take<int>((int64_t)4 * n * m), wk.take<int>((int64_t)4 * n * k),
+          wk.take<void>(region_mix_ws(nullptr, n, c, k).bytes), wk.off};
 }
 
 int bin_launch(const unsigned char* labels, int* perm, int* count, int n, int64_t m, int k, hipStream_t st) {
@@ -717,17 +779,16 @@ int region_cov_launch(const float* x, const int* perm, const int* count, float* 
   return (int)hipGetLastError();
 }
 
-// out from a binned content map and the parts; ws = [valid | mmix | cmix | T]
+// out from a binned content map and the parts
 int region_apply_launch(const float* content, const int* perm, const int* count, const float* cmean, const float* ciroot,
                         const float* smean, const float* sroot, const float* mix, const int* scount, float* out, int n,
-                        int c, int64_t m, int k, int s, int mix_n, int regional, float alpha, unsigned char* ws,
+                        int c, int64_t m, int k, int s, int mix_n, int regional, float alpha, void* wsp,
                         hipStream_t st) {
   const int64_t cc = (int64_t)c * c;
   const int t = tiles_of(c);
-  int* valid = (int*)ws;
-  float* mmix = (float*)(ws + al256((int64_t)4 * n * k));
-  float* cmix = (float*)((unsigned char*)mmix + al256((int64_t)4 * n * k * c));
-  float* T = (float*)((unsigned char*)cmix + al256((int64_t)4 * n * k * cc));
+  const RegionMixWs ws = region_mix_ws(wsp, n, c, k);
+  int* valid = ws.valid;
+  float *mmix = ws.mmix, *cmix = ws.cmix, *T = ws.T;
   hipLaunchKernelGGL(wct_region_mix_kernel, dim3((unsigned)((cc + c + kT - 1) / kT), n * k), dim3(kT), 0, st, sroot, smean,
                      mix, count, scount, cmix, mmix, valid, c, k, s, mix_n == 1 ? 0 : k * s, regional);
   hipLaunchKernelGGL(wct_sq_gemm_kernel<kPlain>, dim3(t, t, n * k), dim3(kT), 0, st, (const float*)cmix, ciroot, T, cc,
@@ -752,6 +813,28 @@ int regions_shape(int n, int c, int hc, int wc, int regions, int styles, int hs,
   e = style_regional ? region_shape(styles, c, hs, ws, regions) : cov_shape(styles, c, (int64_t)hs * ws);
   if (e) return e;
   return n * regions + styles * (style_regional ? regions : 1) > 32767 ? AST_E_SHAPE : AST_OK;
+}
+
+// The whole regional op's workspace: [mean | cov | sqrt | isqrt | content perm, counts | style perm,
+// counts | scratch]: the n * regions content matrices first, then the styles'; the scratch is the
+// covariance partials (the content's, then the styles', regional or plain), then the iteration's
+// buffers, then the apply stage's, each laid out by its stage: stream order keeps them apart
+struct RegionsWs {
+  MatWs mat;
+  int *cperm, *ccount, *sperm, *scount;
+  void* scratch;
+  int64_t bytes;
+};
+
+inline RegionsWs regions_ws(void* base, int n, int c, int64_t mc, int k, int s, int64_t ms, int style_regional) {
+  ast_ws::Walk wk(base);
+  const int b = n * k + s * (style_regional ? k : 1);
+  const int64_t spart = style_regional ? region_part_ws(s, c, ms, k) : cov_ws(s, c, ms);
+  return {mat_ws(wk, b, c), wk.take<int>((int64_t)4 * n * mc), wk.take<int>((int64_t)4 * n * k),
+          wk.take<int>((int64_t)4 * s * ms), wk.take<int>((int64_t)4 * s * k),
+          wk.take<void>(std::max({region_part_ws(n, c, mc, k), spart, sqrt_ws(nullptr, b, c).bytes,
+                                  region_mix_ws(nullptr, n, c, k).bytes})),
+          wk.off};
 }
 
 }  // namespace
@@ -782,7 +865,7 @@ int ast_wct_cov_f32(const float* x, float* mean, float* cov, int n, int c, long 
 long long ast_wct_sqrt_workspace_bytes(int b, int c) {
   if (b <= 0 || c <= 0 || b > 32767) return AST_E_SHAPE;
   if (c > kMaxC) return AST_E_UNSUPPORTED;
-  return sqrt_ws(b, c);
+  return sqrt_ws(nullptr, b, c).bytes;
 }
 
 int ast_wct_sqrt_f32(const float* cov, float* sqrt_or_null, float* isqrt_or_null, int b, int c, int iters,
@@ -790,9 +873,9 @@ int ast_wct_sqrt_f32(const float* cov, float* sqrt_or_null, float* isqrt_or_null
   if (!cov || !workspace || (!sqrt_or_null && !isqrt_or_null)) return AST_E_NULLPTR;
   if (b <= 0 || c <= 0 || b > 32767) return AST_E_SHAPE;
   if (c > kMaxC || iters < 0) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < sqrt_ws(b, c)) return AST_E_SHAPE;
+  if (workspace_bytes < sqrt_ws(nullptr, b, c).bytes) return AST_E_SHAPE;
   if (iters == 0) iters = default_iters(c, 1e-3f);
-  return sqrt_launch(cov, sqrt_or_null, isqrt_or_null, b, c, iters, (unsigned char*)workspace, (hipStream_t)stream);
+  return sqrt_launch(cov, sqrt_or_null, isqrt_or_null, b, c, iters, workspace, (hipStream_t)stream);
 }
 
 long long ast_wct_apply_workspace_bytes(int n, int c) {
@@ -816,10 +899,7 @@ int ast_wct_apply_f32(const float* content, const float* content_mean, const flo
 
 long long ast_wct_workspace_bytes(int n, int ns, int c, long long mc, long long ms) {
   const int e = pair_shape(n, ns, c, mc, ms);
-  if (e) return e;
-  const int b = n + ns;
-  return al256((int64_t)4 * b * c) + 3 * al256((int64_t)4 * b * c * c) +
-         max3(cov_ws(n, c, mc) > cov_ws(ns, c, ms) ? cov_ws(n, c, mc) : cov_ws(ns, c, ms), sqrt_ws(b, c), apply_ws(n, c));
+  return e ? e : wct_ws(nullptr, n, ns, c, mc, ms).bytes;
 }
 
 int ast_wct_f32(const float* content, const float* style, float* out, int n, int ns, int c, int hc, int wc, int hs,
@@ -831,34 +911,28 @@ int ast_wct_f32(const float* content, const float* style, float* out, int n, int
   int e = pair_shape(n, ns, c, mc, ms);
   if (e) return e;
   if (!eps_ok(eps_rel) || iters < 0) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < ast_wct_workspace_bytes(n, ns, c, mc, ms)) return AST_E_SHAPE;
+  const WctWs w = wct_ws(workspace, n, ns, c, mc, ms);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   if (iters == 0) iters = default_iters(c, eps_rel);
   hipStream_t st = (hipStream_t)stream;
-  // [mean | cov | sqrt | isqrt | scratch], content samples first, then the style's; the scratch is
-  // the covariance partials, then the iteration's buffers, then T: stream order keeps them apart
   const int b = n + ns;
-  const int64_t cc = (int64_t)c * c, mb = al256((int64_t)4 * b * cc);
-  unsigned char* w = (unsigned char*)workspace;
-  float* mean = (float*)w;
-  float* cov = (float*)(w + al256((int64_t)4 * b * c));
-  float* root = (float*)((unsigned char*)cov + mb);
-  float* iroot = (float*)((unsigned char*)root + mb);
-  unsigned char* scratch = (unsigned char*)iroot + mb;
-  e = cov_launch(content, mean, cov, n, c, mc, eps_rel, (float*)scratch, st);
+  const int64_t cc = (int64_t)c * c;
+  float *mean = w.mat.mean, *cov = w.mat.cov, *root = w.mat.root, *iroot = w.mat.iroot;
+  e = cov_launch(content, mean, cov, n, c, mc, eps_rel, (float*)w.scratch, st);
   if (e) return e;
-  e = cov_launch(style, mean + (int64_t)n * c, cov + n * cc, ns, c, ms, eps_rel, (float*)scratch, st);
+  e = cov_launch(style, mean + (int64_t)n * c, cov + n * cc, ns, c, ms, eps_rel, (float*)w.scratch, st);
   if (e) return e;
-  e = sqrt_launch(cov, root, iroot, b, c, iters, scratch, st);
+  e = sqrt_launch(cov, root, iroot, b, c, iters, w.scratch, st);
   if (e) return e;
   return apply_launch(content, mean, mean + (int64_t)n * c, root + n * cc, iroot, out, n, ns, c, mc, (float)alpha,
-                      (float*)scratch, st);
+                      (float*)w.scratch, st);
 }
 
 // ---- regional WCT ----
 
 long long ast_wct_region_cov_workspace_bytes(int n, int c, int h, int w, int regions) {
   const int e = region_shape(n, c, h, w, regions);
-  return e ? e : region_cov_ws(n, c, (int64_t)h * w, regions);
+  return e ? e : region_cov_ws(nullptr, n, c, (int64_t)h * w, regions).bytes;
 }
 
 int ast_wct_region_cov_f32(const float* x, const unsigned char* labels, float* mean, float* cov, int* count, int n,
@@ -869,18 +943,17 @@ int ast_wct_region_cov_f32(const float* x, const unsigned char* labels, float* m
   if (e) return e;
   if (!eps_ok(eps_rel)) return AST_E_UNSUPPORTED;
   const int64_t m = (int64_t)h * w;
-  if (workspace_bytes < region_cov_ws(n, c, m, regions)) return AST_E_SHAPE;
+  const RegionCovWs s = region_cov_ws(workspace, n, c, m, regions);
+  if (workspace_bytes < s.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  int* perm = (int*)workspace;
-  e = bin_launch(labels, perm, count, n, m, regions, st);
+  e = bin_launch(labels, s.perm, count, n, m, regions, st);
   if (e) return e;
-  return region_cov_launch(x, perm, count, mean, cov, n, c, m, regions, eps_rel,
-                           (float*)((unsigned char*)workspace + perm_ws(n, m)), st);
+  return region_cov_launch(x, s.perm, count, mean, cov, n, c, m, regions, eps_rel, s.part, st);
 }
 
 long long ast_wct_region_apply_workspace_bytes(int n, int c, int h, int w, int regions) {
   const int e = region_shape(n, c, h, w, regions);
-  return e ? e : region_apply_ws(n, c, (int64_t)h * w, regions);
+  return e ? e : region_apply_ws(nullptr, n, c, (int64_t)h * w, regions).bytes;
 }
 
 int ast_wct_region_apply_f32(const float* content, const unsigned char* labels, const float* content_mean,
@@ -895,30 +968,20 @@ int ast_wct_region_apply_f32(const float* content, const unsigned char* labels, 
   e = mix_shape(n, styles, mix_n);
   if (e) return e;
   const int64_t m = (int64_t)h * w;
-  if (workspace_bytes < region_apply_ws(n, c, m, regions)) return AST_E_SHAPE;
+  const RegionApplyWs s = region_apply_ws(workspace, n, c, m, regions);
+  if (workspace_bytes < s.bytes) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* wsp = (unsigned char*)workspace;
-  int* perm = (int*)wsp;
-  int* count = (int*)(wsp + perm_ws(n, m));
-  e = bin_launch(labels, perm, count, n, m, regions, st);
+  e = bin_launch(labels, s.perm, s.count, n, m, regions, st);
   if (e) return e;
-  return region_apply_launch(content, perm, count, content_mean, content_isqrt, style_mean, style_sqrt, mix,
+  return region_apply_launch(content, s.perm, s.count, content_mean, content_isqrt, style_mean, style_sqrt, mix,
                              style_regional ? style_count_or_null : nullptr, out, n, c, m, regions, styles, mix_n,
-                             style_regional ? 1 : 0, (float)alpha, wsp + perm_ws(n, m) + al256((int64_t)4 * n * regions),
-                             st);
+                             style_regional ? 1 : 0, (float)alpha, s.mix, st);
 }
 
 long long ast_wct_regions_workspace_bytes(int n, int c, int hc, int wc, int regions, int styles, int hs, int ws,
                                           int style_regional) {
   const int e = regions_shape(n, c, hc, wc, regions, styles, hs, ws, style_regional, 1);
-  if (e) return e;
-  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws;
-  const int b = n * regions + styles * (style_regional ? regions : 1);
-  const int64_t spart = style_regional ? region_part_ws(styles, c, ms, regions) : cov_ws(styles, c, ms);
-  const int64_t part = region_part_ws(n, c, mc, regions) > spart ? region_part_ws(n, c, mc, regions) : spart;
-  return al256((int64_t)4 * b * c) + 3 * al256((int64_t)4 * b * c * c) + perm_ws(n, mc) +
-         al256((int64_t)4 * n * regions) + perm_ws(styles, ms) + al256((int64_t)4 * styles * regions) +
-         max3(part, sqrt_ws(b, c), region_mix_ws(n, c, regions));
+  return e ? e : regions_ws(nullptr, n, c, (int64_t)hc * wc, regions, styles, (int64_t)hs * ws, style_regional).bytes;
 }
 
 int ast_wct_regions_f32(const float* content, const unsigned char* labels, const float* styles,
@@ -930,42 +993,31 @@ int ast_wct_regions_f32(const float* content, const unsigned char* labels, const
   int e = regions_shape(n, c, hc, wc, regions, s, hs, ws, reg, mix_n);
   if (e) return e;
   if (!eps_ok(eps_rel) || iters < 0) return AST_E_UNSUPPORTED;
-  if (workspace_bytes < ast_wct_regions_workspace_bytes(n, c, hc, wc, regions, s, hs, ws, reg)) return AST_E_SHAPE;
+  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws, cc = (int64_t)c * c;
+  const RegionsWs w = regions_ws(workspace, n, c, mc, regions, s, ms, reg);
+  if (workspace_bytes < w.bytes) return AST_E_SHAPE;
   if (iters == 0) iters = default_iters(c, eps_rel);
   hipStream_t st = (hipStream_t)stream;
-  // [mean | cov | sqrt | isqrt | content perm, counts | style perm, counts | scratch]: the n * regions
-  // content matrices first, then the styles'; the scratch is the covariance partials, then the
-  // iteration's buffers, then the apply stage's: stream order keeps them apart
-  const int64_t mc = (int64_t)hc * wc, ms = (int64_t)hs * ws, cc = (int64_t)c * c;
   const int nk = n * regions, b = nk + s * (reg ? regions : 1);
-  const int64_t mb = al256((int64_t)4 * b * cc);
-  unsigned char* w = (unsigned char*)workspace;
-  float* mean = (float*)w;
-  float* cov = (float*)(w + al256((int64_t)4 * b * c));
-  float* root = (float*)((unsigned char*)cov + mb);
-  float* iroot = (float*)((unsigned char*)root + mb);
-  int* cperm = (int*)((unsigned char*)iroot + mb);
-  int* ccount = (int*)((unsigned char*)cperm + perm_ws(n, mc));
-  int* sperm = (int*)((unsigned char*)ccount + al256((int64_t)4 * nk));
-  int* scount = (int*)((unsigned char*)sperm + perm_ws(s, ms));
-  unsigned char* scratch = (unsigned char*)scount + al256((int64_t)4 * s * regions);
+  float *mean = w.mat.mean, *cov = w.mat.cov, *root = w.mat.root, *iroot = w.mat.iroot;
+  int *cperm = w.cperm, *ccount = w.ccount, *sperm = w.sperm, *scount = w.scount;
   e = bin_launch(labels, cperm, ccount, n, mc, regions, st);
   if (e) return e;
-  e = region_cov_launch(content, cperm, ccount, mean, cov, n, c, mc, regions, eps_rel, (float*)scratch, st);
+  e = region_cov_launch(content, cperm, ccount, mean, cov, n, c, mc, regions, eps_rel, (float*)w.scratch, st);
   if (e) return e;
   float* smean = mean + (int64_t)nk * c;
   if (reg) {
     e = bin_launch(style_labels_or_null, sperm, scount, s, ms, regions, st);
     if (e) return e;
-    e = region_cov_launch(styles, sperm, scount, smean, cov + nk * cc, s, c, ms, regions, eps_rel, (float*)scratch, st);
+    e = region_cov_launch(styles, sperm, scount, smean, cov + nk * cc, s, c, ms, regions, eps_rel, (float*)w.scratch, st);
   } else {
-    e = cov_launch(styles, smean, cov + nk * cc, s, c, ms, eps_rel, (float*)scratch, st);
+    e = cov_launch(styles, smean, cov + nk * cc, s, c, ms, eps_rel, (float*)w.scratch, st);
   }
   if (e) return e;
-  e = sqrt_launch(cov, root, iroot, b, c, iters, scratch, st);
+  e = sqrt_launch(cov, root, iroot, b, c, iters, w.scratch, st);
   if (e) return e;
   return region_apply_launch(content, cperm, ccount, mean, iroot, smean, root + nk * cc, mix, reg ? scount : nullptr, out,
-                             n, c, mc, regions, s, mix_n, reg, (float)alpha, scratch, st);
+                             n, c, mc, regions, s, mix_n, reg, (float)alpha, w.scratch, st);
 }
 
 }  // extern "C"
