@@ -98,6 +98,16 @@ SIGNATURES = {
     "ast_selfsim_loss_f32": (_i, [_p] * 11 + [_i, _i, _i, _f, _p, _ll, _p]),
     "ast_selfsim_loss_backward_workspace_bytes": (_ll, [_i, _i, _i]),
     "ast_selfsim_loss_backward_f32": (_i, [_p] * 8 + [_i, _i, _i, _f, _p, _ll, _p]),
+    "ast_cx_center_f32": (_i, [_p] * 5 + [_i] * 5 + [_p]),
+    "ast_cx_rowsum_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
+    "ast_cx_rowsum_f32": (_i, [_p] * 7 + [_i] * 5 + [_f, _i, _p, _ll, _p]),
+    "ast_cx_colmax_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "ast_cx_colmax_f32": (_i, [_p] * 9 + [_i] * 5 + [_f, _i, _p, _ll, _p]),
+    "ast_cx_value_f32": (_i, [_p, _p, _p, _i, _i, _f, _p]),
+    "ast_cx_loss_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "ast_cx_loss_f32": (_i, [_p] * 16 + [_i] * 5 + [_f, _f, _i, _p, _ll, _p]),
+    "ast_cx_loss_backward_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "ast_cx_loss_backward_f32": (_i, [_p] * 13 + [_i] * 5 + [_f, _f, _p, _ll, _p]),
     "ast_kmeans_workspace_bytes":(_ll, [_i, _i, _i, _i, _i]),
     "ast_kmeans_seed_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "ast_kmeans_assign_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -734,6 +734,25 @@ class SelfSimLossFn(torch.autograd.Function):
         return ops.selfsim_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None
 
 
+class CxLossFn(torch.autograd.Function):
+    """weight * the contextual loss between the pixels of x and of y (ops.cx_loss), bandwidth h, centred on
+    y's channel means unless center is off; y is data (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, h=0.5, center=True):
+        x, y = _dev(x, "t_cs_map"), _dev(y, "target_map")
+        loss, _, state = ops.cx_loss(x, y, float(weight), float(h), bool(center), acc=_acc(x))
+        ctx.save_for_backward(x, y, *state)
+        ctx.weight, ctx.h = float(weight), float(h)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, *state = ctx.saved_tensors
+        dx = ops.cx_loss_backward(x, y, tuple(state), _dev(g, "grad"), ctx.weight, ctx.h)
+        return dx, None, None, None, None
+
+
 class RangeLossFn(torch.autograd.Function):
     """weight * compute_content_loss(x, torch.clip(x.detach(), 0, 1)) (train.py:259)."""
 

@@ -23,6 +23,7 @@ tv_loss                 losses.py:90-103                             d img
 hist_loss               losses.py:84-87 (SingleDimHist + EMD)        d x
 remd_loss               -- (relaxed EMD: two-way cosine match)       d x
 selfsim_loss            -- (self-similarity of pixel-pair distances) d x
+cx_loss                 -- (contextual loss: softmax over a cosine match) d x
 range_loss              train.py:259                                 d x
 sqdiff_mean             train.py:268                                 d x
 mb_expand_dw            mobilenetv2.py:153-161 (to the SE pool)      -- (eval BN folded: inference)
@@ -503,6 +504,40 @@ def _selfsim_backward(ctx, g, *_):
 register_autograd("ast_hip::selfsim_loss", _selfsim_backward, setup_context=_selfsim_setup)
 
 
+@custom_op("ast_hip::cx_loss", mutates_args=())
+def cx_loss(x: Tensor, y: Tensor, weight: float, h: float, center: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor,
+                                                                                 Tensor, Tensor, Tensor, Tensor, Tensor,
+                                                                                 Tensor, Tensor, Tensor]:
+    """weight * the contextual loss of ops.cx_loss; outputs (loss, xc, yc, inv_x, inv_y, row_min, row_index,
+    row_sum, row_dsum, col_cx, col_index, col_dist, per_sample_cx); xc and yc are empty when center is off."""
+    loss, _, state = ops.cx_loss(x, y, float(weight), float(h), bool(center), acc=_acc(x))
+    return (loss,) + tuple(state)
+
+
+@register_fake("ast_hip::cx_loss")
+def _(x, y, weight, h, center):
+    n, (hh, ww), (hs, ws) = x.shape[0], x.shape[2:], y.shape[2:]
+    i32 = dict(dtype=torch.int32)
+    xc, yc = (torch.empty_like(x), torch.empty_like(y)) if center else (x.new_empty((0,)), x.new_empty((0,)))
+    return (x.new_empty(()), xc, yc, x.new_empty((n, hh, ww)), x.new_empty((y.shape[0], hs, ws)),
+            x.new_empty((n, hh, ww)), x.new_empty((n, hh, ww), **i32), x.new_empty((n, hh, ww)),
+            x.new_empty((n, hh, ww)), x.new_empty((n, hs, ws)), x.new_empty((n, hs, ws), **i32),
+            x.new_empty((n, hs, ws)), x.new_empty((n,)))
+
+
+def _cx_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], *output[1:])
+    ctx.weight, ctx.h = float(inputs[2]), float(inputs[3])
+
+
+def _cx_backward(ctx, g, *_):
+    x, y, *state = ctx.saved_tensors
+    return ops.cx_loss_backward(x, y, tuple(state), g.contiguous(), ctx.weight, ctx.h), None, None, None, None
+
+
+register_autograd("ast_hip::cx_loss", _cx_backward, setup_context=_cx_setup)
+
+
 @custom_op("ast_hip::range_loss", mutates_args=())
 def range_loss(x: Tensor, weight: float) -> Tensor:
     acc = _acc(x)
@@ -948,7 +983,7 @@ def _(labels, regions, passes):
 
 
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
-                  "remd_loss", "selfsim_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw",
+                  "remd_loss", "selfsim_loss", "cx_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw",
                   "mb_expand_gemm", "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer",
                   "resize_labels",
                   "region_stats", "adain_regions", "efdm", "plane_sort", "efdm_regions", "wct", "wct_regions",

@@ -62,7 +62,7 @@ __all__ = ["gram_matrix", "compute_content_loss", "compute_style_loss", "tv_loss
            "content_mvn_loss", "style_loss_weighted", "content_style_loss", "EarthMoversDistanceLoss",
            "HistLayerBase",
            "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss",
-           "compute_efdm_loss", "compute_remd_loss", "compute_selfsim_loss"]
+           "compute_efdm_loss", "compute_remd_loss", "compute_selfsim_loss", "compute_contextual_loss"]
 
 
 def gram_matrix(tensor):
@@ -185,6 +185,17 @@ def compute_selfsim_loss(t_cs_map, content_map, weight: float = 1.0):
     gradient reaches t_cs_map through the HIP backward (torch.ops.ast_hip.selfsim_loss)."""
     x, c = _dev(t_cs_map, "t_cs_map"), _dev(content_map.detach(), "content_map")
     return _ops.selfsim_loss(x, c, float(weight))[0]
+
+
+def compute_contextual_loss(t_cs_map, target_map, weight: float = 1.0, h: float = 0.5, center: bool = True):
+    """The contextual loss of one loss tap (Mechrez, Talmi, Zelnik-Manor, ECCV 2018), exact: with D the cosine
+    distance between every pixel of t_cs_map [N, C, H, W] and every pixel of target_map [N or 1, C, Ht, Wt]
+    (any size; both centred on the target's channel means unless center is off), each row divided by its
+    minimum and passed through a softmax of bandwidth h, weight * mean over the batch of -log mean_j max_i
+    CX(i, j). The target (a style map, or a content map) is detached; the gradient reaches t_cs_map through
+    the HIP backward (torch.ops.ast_hip.cx_loss)."""
+    x, y = _dev(t_cs_map, "t_cs_map"), _dev(target_map.detach(), "target_map")
+    return _ops.cx_loss(x, y, float(weight), float(h), bool(center))[0]
 
 
 def out_of_range_loss(img, weight: float = 1e8):

@@ -1033,6 +1033,169 @@ def selfsim_loss_backward(x: torch.Tensor, state, grad: torch.Tensor, weight: fl
     return dx
 
 
+# Contextual loss (csrc/cx.hip): the limits of ast_hip.h
+CX_MAX_C = 1024
+CX_MAX_PIXELS = 1 << 14
+CX_EPS = 1e-5
+
+
+def _cx_pair(x: torch.Tensor, y: torch.Tensor, what: str, h: float = 0.5):
+    """The checks of _remd_pair inside the limits of csrc/cx.hip, and a positive finite bandwidth:
+    (x, y, n, ns, c, m, p)."""
+    x, y, n, ns, c, m, p = _remd_pair(x, y, what)
+    if c > CX_MAX_C or max(m, p) > CX_MAX_PIXELS:
+        raise HipOpError(f"{what}: C is at most {CX_MAX_C} and a map has at most {CX_MAX_PIXELS} pixels: "
+                         f"x {tuple(x.shape)} vs y {tuple(y.shape)}")
+    h = float(h)
+    if not (h > 0.0) or h == float("inf"):
+        raise HipOpError(f"{what}: the bandwidth h must be positive and finite, got {h}")
+    return x, y, n, ns, c, m, p
+
+
+def _cx_like(t, dev, numel: int, dtype, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.numel() != numel:
+        raise HipOpError(f"{what} must be a {dtype} tensor of {numel} elements on {dev}")
+    return t.contiguous()
+
+
+def cx_center(x: torch.Tensor, y: torch.Tensor):
+    """(mu [Ns, C], xc, yc): the channel means of y [N or 1, C, Hs, Ws] over its pixels, summed in a fixed
+    order, and both maps with them subtracted: the centring of the contextual loss."""
+    x, y, n, ns, c, m, p = _cx_pair(x, y, "cx_center")
+    mu = torch.empty((ns, c), device=x.device, dtype=torch.float32)
+    xc, yc = torch.empty_like(x), torch.empty_like(y)
+    check(lib().ast_cx_center_f32(ptr(x), ptr(y), ptr(mu), ptr(xc), ptr(yc), n, ns, c, m, p, stream_ptr(x.device)),
+          "cx_center")
+    return mu, xc, yc
+
+
+def _cx_rows(x, y, inv_x, inv_y, row_min, what, n, ns, m, p):
+    dev, f = x.device, torch.float32
+    return (_cx_like(inv_x, dev, n * m, f, f"{what}: inv_x"), _cx_like(inv_y, dev, ns * p, f, f"{what}: inv_y"),
+            _cx_like(row_min, dev, n * m, f, f"{what}: row_min"))
+
+
+def cx_rowsum(xc: torch.Tensor, yc: torch.Tensor, inv_x: torch.Tensor, inv_y: torch.Tensor, row_min: torch.Tensor,
+              h: float = 0.5, _splits: int = 0):
+    """(S, E) [N, H, W] of the contextual loss: with D the cosine distances of cosine_match(xc, yc), r its
+    row minima and w(i, j) = exp((1 - D(i, j) / (r_i + eps)) / h), S_i = sum_j w(i, j) and E_i = sum_j w(i, j)
+    D(i, j). The distances are never stored. _splits as in cosine_match."""
+    x, y, n, ns, c, m, p = _cx_pair(xc, yc, "cx_rowsum", h)
+    u, v, r = _cx_rows(x, y, inv_x, inv_y, row_min, "cx_rowsum", n, ns, m, p)
+    L, dev = lib(), x.device
+    nb = int(L.ast_cx_rowsum_workspace_bytes(n, ns, m, p, int(_splits)))
+    wsb = _ws_bytes(nb, "cx_rowsum workspace", dev)
+    S = torch.empty((n,) + tuple(x.shape[2:]), device=dev, dtype=torch.float32)
+    E = torch.empty_like(S)
+    check(_timed(f"cx_rowsum {c}ch {m} vs {p}", 2 * n * m * p * c, dev, lambda: L.ast_cx_rowsum_f32(
+        ptr(x), ptr(y), ptr(u), ptr(v), ptr(r), ptr(S), ptr(E), n, ns, c, m, p, float(h), int(_splits), ptr(wsb), nb,
+        stream_ptr(dev))), "cx_rowsum")
+    return S, E
+
+
+def cx_colmax(xc: torch.Tensor, yc: torch.Tensor, inv_x: torch.Tensor, inv_y: torch.Tensor, row_min: torch.Tensor,
+              row_sum: torch.Tensor, h: float = 0.5, _splits: int = 0):
+    """(col_cx [N, Hs, Ws], col_index int32, col_dist): c_j = max_i w(i, j) / S_i, its arg-max (the lowest
+    index on equal values, a NaN never wins) and the distance D(a_j, j) there. Bit-equal for every
+    _splits."""
+    x, y, n, ns, c, m, p = _cx_pair(xc, yc, "cx_colmax", h)
+    u, v, r = _cx_rows(x, y, inv_x, inv_y, row_min, "cx_colmax", n, ns, m, p)
+    S = _cx_like(row_sum, x.device, n * m, torch.float32, "cx_colmax: row_sum")
+    L, dev = lib(), x.device
+    nb = int(L.ast_cx_colmax_workspace_bytes(n, ns, m, p))
+    wsb = _ws_bytes(nb, "cx_colmax workspace", dev)
+    shp = (n,) + tuple(y.shape[2:])
+    ccx = torch.empty(shp, device=dev, dtype=torch.float32)
+    cidx = torch.empty(shp, device=dev, dtype=torch.int32)
+    cdist = torch.empty_like(ccx)
+    check(_timed(f"cx_colmax {c}ch {m} vs {p}", 2 * n * m * p * c, dev, lambda: L.ast_cx_colmax_f32(
+        ptr(x), ptr(y), ptr(u), ptr(v), ptr(r), ptr(S), ptr(ccx), ptr(cidx), ptr(cdist), n, ns, c, m, p, float(h),
+        int(_splits), ptr(wsb), nb, stream_ptr(dev))), "cx_colmax")
+    return ccx, cidx, cdist
+
+
+def cx_value(col_cx: torch.Tensor, weight: float = 1.0, acc=None):
+    """(loss, per_sample_cx [N]) from the column maxima of cx_colmax: CX_b = mean_j c_j, loss = weight *
+    mean_b -log CX_b: the last stage of cx_loss. `acc`: the loss accumulator the value is added into."""
+    if (not isinstance(col_cx, torch.Tensor) or col_cx.device.type != "cuda" or col_cx.dtype != torch.float32
+            or col_cx.dim() < 2 or col_cx.numel() == 0):
+        raise HipOpError("cx_value needs the float32 device column maxima [N, ...] of cx_colmax")
+    col_cx, dev, n = col_cx.contiguous(), col_cx.device, int(col_cx.shape[0])
+    cxb = torch.empty((n,), device=dev, dtype=torch.float32)
+    acc = loss_accumulator(dev) if acc is None else acc
+    check(lib().ast_cx_value_f32(ptr(col_cx), ptr(cxb), ptr(acc), n, col_cx.numel() // n, float(weight),
+                                 stream_ptr(dev)), "cx_value")
+    return acc[0], cxb
+
+
+def cx_loss(x: torch.Tensor, y: torch.Tensor, weight: float = 1.0, h: float = 0.5, center: bool = True, acc=None):
+    """The contextual loss (Mechrez et al., ECCV 2018), exact: weight * mean over the batch of -log CX_b,
+    CX_b = mean_j max_i softmax-like CX(i, j) of the cosine distances between the pixels of x [N, C, H, W]
+    (the differentiable side) and y [N or 1, C, Hs, Ws], normalised per row by the row minimum, bandwidth h;
+    center subtracts y's channel means from both maps first. Returns (loss, per_sample_cx [N], state); state
+    = (xc, yc, inv_x, inv_y, row_min, row_index, row_sum, row_dsum, col_cx, col_index, col_dist, per_sample_cx)
+    is what cx_loss_backward reads; xc and yc are empty when center is off (the maps themselves are used).
+    No M x P tensor is stored."""
+    x, y, n, ns, c, m, p = _cx_pair(x, y, "cx_loss", h)
+    L, dev = lib(), x.device
+    nb = int(L.ast_cx_loss_workspace_bytes(n, ns, m, p))
+    wsb = _ws_bytes(nb, "cx_loss workspace", dev)
+    (hh, ww), (hs, ws) = x.shape[2:], y.shape[2:]
+    f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+    if center:
+        mu, xc, yc = torch.empty((ns, c), **f32), torch.empty_like(x), torch.empty_like(y)
+    else:
+        mu, xc, yc = None, torch.empty((0,), **f32), torch.empty((0,), **f32)
+    u, v = torch.empty((n, hh, ww), **f32), torch.empty((ns, hs, ws), **f32)
+    rmin, ridx = torch.empty((n, hh, ww), **f32), torch.empty((n, hh, ww), **i32)
+    S, E = torch.empty((n, hh, ww), **f32), torch.empty((n, hh, ww), **f32)
+    ccx, cidx, cdist = torch.empty((n, hs, ws), **f32), torch.empty((n, hs, ws), **i32), torch.empty((n, hs, ws), **f32)
+    cxb = torch.empty((n,), **f32)
+    acc = loss_accumulator(dev) if acc is None else acc
+    pc = (lambda t: ptr(t)) if center else (lambda t: None)
+    check(_timed(f"cx_loss {c}ch {m} vs {p}", 6 * n * m * p * c, dev, lambda: L.ast_cx_loss_f32(
+        ptr(x), ptr(y), pc(mu), pc(xc), pc(yc), ptr(u), ptr(v), ptr(rmin), ptr(ridx), ptr(S), ptr(E), ptr(ccx),
+        ptr(cidx), ptr(cdist), ptr(cxb), ptr(acc), n, ns, c, m, p, float(weight), float(h), 1 if center else 0,
+        ptr(wsb), nb, stream_ptr(dev))), "cx_loss")
+    return acc[0], cxb, (xc, yc, u, v, rmin, ridx, S, E, ccx, cidx, cdist, cxb)
+
+
+def cx_loss_backward(x: torch.Tensor, y: torch.Tensor, state, grad: torch.Tensor, weight: float = 1.0,
+                     h: float = 0.5) -> torch.Tensor:
+    """d loss / d x [N, C, H, W] of cx_loss from its state, scaled by the device scalar `grad`; nothing flows
+    to y. The inverse lists of the column arg-maxima, the row scalars, then a dense pass that recomputes
+    the distances and the weights tile by tile and a finishing pass."""
+    x, y, n, ns, c, m, p = _cx_pair(x, y, "cx_loss_backward", h)
+    if not isinstance(state, (tuple, list)) or len(state) != 12:
+        raise HipOpError("cx_loss_backward needs the state of cx_loss (12 tensors)")
+    dev, f, what = x.device, torch.float32, "cx_loss_backward: {}"
+    xc, yc = state[0], state[1]
+    if isinstance(xc, torch.Tensor) and xc.numel() == 0 and isinstance(yc, torch.Tensor) and yc.numel() == 0:
+        xc, yc = x, y   # center was off
+    xc = _cx_like(xc, dev, x.numel(), f, what.format("xc"))
+    yc = _cx_like(yc, dev, y.numel(), f, what.format("yc"))
+    u = _cx_like(state[2], dev, n * m, f, what.format("inv_x"))
+    v = _cx_like(state[3], dev, ns * p, f, what.format("inv_y"))
+    rmin = _cx_like(state[4], dev, n * m, f, what.format("row_min"))
+    ridx = _cx_like(state[5], dev, n * m, torch.int32, what.format("row_index"))
+    S = _cx_like(state[6], dev, n * m, f, what.format("row_sum"))
+    E = _cx_like(state[7], dev, n * m, f, what.format("row_dsum"))
+    cidx = _cx_like(state[9], dev, n * p, torch.int32, what.format("col_index"))
+    cdist = _cx_like(state[10], dev, n * p, f, what.format("col_dist"))
+    cxb = _cx_like(state[11], dev, n, f, what.format("per_sample_cx"))
+    grad = _cx_like(grad, dev, 1, f, what.format("grad"))
+    L = lib()
+    nb = int(L.ast_cx_loss_backward_workspace_bytes(n, c, m, p))
+    wsb = _ws_bytes(nb, "cx_loss_backward workspace", dev)
+    dx = torch.empty_like(x)
+    flops = 2 * n * m * p * c * ((c + 511) // 512 + 1)
+    check(_timed(f"cx_loss_backward {c}ch {m} vs {p}", flops, dev, lambda: L.ast_cx_loss_backward_f32(
+        ptr(xc), ptr(yc), ptr(u), ptr(v), ptr(rmin), ptr(ridx), ptr(S), ptr(E), ptr(cidx), ptr(cdist), ptr(cxb),
+        ptr(grad), ptr(dx), n, ns, c, m, p, float(weight), float(h), ptr(wsb), nb, stream_ptr(dev))),
+        "cx_loss_backward")
+    return dx
+
+
 # Guided style swap (csrc/swap.hip): a class >= SWAP_MAX_CLASSES takes no part in the match
 SWAP_MAX_CLASSES = 64
 _SWAP_NO_SKIP = 1   # AST_SWAP_NO_SKIP

@@ -27,6 +27,12 @@ With `selfsim_lam > 0` (an extension likewise) it adds the self-similarity conte
 between the stylised and the content features at `selfsim_taps` (losses.compute_selfsim_loss):
   loss        += selfsim_lam * sum_taps selfsim(lossnet(stylised)[tap], lossnet(content)[tap])
 a batch-mean term too; at the default selfsim_lam = 0 nothing is launched.
+With `cx_lam > 0` (an extension likewise) it adds the contextual loss (losses.compute_contextual_loss, bandwidth
+`cx_h`) between the stylised and the style features at `cx_taps`, with `cx_content_lam > 0` the same loss
+against the content features at `cx_content_taps`:
+  loss        += cx_lam * sum_taps cx(lossnet(stylised)[tap], lossnet(style)[tap])
+  loss        += cx_content_lam * sum_taps cx(lossnet(stylised)[tap], lossnet(content)[tap])
+batch-mean terms; at the defaults of 0 nothing is launched.
 
 Data parallel (config 4): one process per GPU, each with its own shard of the global batch
 (`args.batch_size` is the global batch, as the reference's --batch_size is the batch of one step;
@@ -150,6 +156,12 @@ REMD_TAPS = ("relu_9", "relu_15")
 SELFSIM_TAPS = ("relu_9", "relu_15")
 
 
+# The taps of the contextual terms (losses.compute_contextual_loss): against the style at both maps, against
+# the content at relu5_1; a tap's map may have at most ops.CX_MAX_PIXELS pixels.
+CX_TAPS = ("relu_9", "relu_15")
+CX_CONTENT_TAPS = ("relu_15",)
+
+
 def _tap_index(name, arg="remd_taps"):
     if name not in _TAPS:
         raise ValueError(f"{arg}: {name!r} is not a tap of the loss network {_TAPS}")
@@ -159,7 +171,8 @@ def _tap_index(name, arg="remd_taps"):
 def default_args(**kw):
     a = dict(train_iter=10, batch_size=8, lr=2e-4, content_lam=1.25, style_lam=0.5, tv_lam=0.0006, lf_lam=1.0,
              org_img_lam=0.5, save_dir="models/ast/", load=False, image_size=512, full_losses=False,
-             remd_lam=0.0, remd_taps=REMD_TAPS, selfsim_lam=0.0, selfsim_taps=SELFSIM_TAPS)
+             remd_lam=0.0, remd_taps=REMD_TAPS, selfsim_lam=0.0, selfsim_taps=SELFSIM_TAPS,
+             cx_lam=0.0, cx_taps=CX_TAPS, cx_content_lam=0.0, cx_content_taps=CX_CONTENT_TAPS, cx_h=0.5)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -240,6 +253,21 @@ class AdaINTrainer:
             mean_terms = mean_terms + selfsim_lam * selfsim_loss
             loss = loss + selfsim_lam * selfsim_loss
             out.update(loss=loss, selfsim_loss=selfsim_loss)
+        cx_lam, cx_content_lam = float(getattr(a, "cx_lam", 0.0)), float(getattr(a, "cx_content_lam", 0.0))
+        cx_h = float(getattr(a, "cx_h", 0.5))
+        if cx_lam > 0:   # the contextual style term; nothing is launched without it
+            cx_idx = [_tap_index(k, "cx_taps") for k in getattr(a, "cx_taps", CX_TAPS)]
+            cx_loss = torch.stack([L.compute_contextual_loss(s_taps[i], taps[i][b:], 1.0, cx_h) for i in cx_idx]).sum()
+            mean_terms = mean_terms + cx_lam * cx_loss
+            loss = loss + cx_lam * cx_loss
+            out.update(loss=loss, cx_loss=cx_loss)
+        if cx_content_lam > 0:   # the contextual content term
+            cxc_idx = [_tap_index(k, "cx_content_taps") for k in getattr(a, "cx_content_taps", CX_CONTENT_TAPS)]
+            cx_content_loss = torch.stack([L.compute_contextual_loss(s_taps[i], taps[i][:b], 1.0, cx_h)
+                                           for i in cxc_idx]).sum()
+            mean_terms = mean_terms + cx_content_lam * cx_content_loss
+            loss = loss + cx_content_lam * cx_content_loss
+            out.update(loss=loss, cx_content_loss=cx_content_loss)
         if getattr(a, "full_losses", False):
             org_out = self.net.decoder(f_c)
             o_taps = self.lossnet(org_out)

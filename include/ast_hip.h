@@ -641,6 +641,91 @@ int ast_selfsim_loss_backward_f32(const float* x, const float* inv_x, const floa
                                   float* dx, int n, int c, int pixels, float weight, void* workspace,
                                   long long workspace_bytes, void* stream);
 
+/* Contextual loss (Mechrez, Talmi, Zelnik-Manor, ECCV 2018; csrc/cx.hip; an extension, no reference
+ * counterpart): the soft counterpart of the relaxed EMD above, on the same pairwise cosine distances,
+ * exact, without ever storing an m x p tensor. tests/cx_ref.py restates the definition.
+ * Inputs, fp32 NCHW with the spatial sides flattened: x [n, c, m], the stylised map and the
+ * differentiable side; y [ns, c, p], ns = n or 1, data (no gradient); h > 0, the bandwidth, a runtime
+ * float; eps = AST_CX_EPS. Limits: c in 1..AST_CX_MAX_C, m and p in 1..AST_CX_MAX_PIXELS, n <= 65535.
+ * Centring (center != 0, the authors' default): mu[c] = mean_j y[c, j], summed in a fixed order;
+ *   xc = x - mu, yc = y - mu. With center == 0, xc = x and yc = y and mu, xc, yc may be null.
+ * Distances: u_i, v_j and D(i, j) = 1 - (<xc_i, yc_j> u_i) v_j are those of ast_cosine_norms_f32 /
+ *   ast_cosine_match_f32 on (xc, yc), bit for bit: the same inverse-norm rule, the same fma chain, a
+ *   zero vector at distance 1 from everything. No clamp: eps keeps r_i + eps positive.
+ * Row side: r_i = min_j D(i, j) with arg-min m_i (ast_cosine_match_f32 as it is); k_i = 1 / (r_i + eps);
+ *   w(i, j) = exp((1 - D(i, j) k_i) / h);  S_i = sum_j w(i, j);  E_i = sum_j w(i, j) D(i, j).
+ * Column side: CX(i, j) = w(i, j) / S_i; c_j = max_i CX(i, j) with arg-max a_j, the lowest index on
+ *   equal values; a NaN never wins; without a winner the pair stays (-inf, 0).
+ * Loss: CX_b = (1 / p) sum_j c_j, summed in a fixed order; *loss += weight / n * sum_b -log CX_b, the
+ *   samples in sample order, into the loss accumulator (ast_loss_acc_floats).
+ * Gradient, to x only, g = *grad_scale; xh_i = u_i xc_i, yh_j = v_j yc_j; J_i = { j : a_j = i }, ascending:
+ *   A_i = sum_{j in J_i} w(i, j);  B_i = sum_{j in J_i} w(i, j) D(i, j);  T_i = B_i / S_i - A_i E_i / S_i^2
+ *   G_i = (k_i / (h S_i)) (sum_{j in J_i} w(i, j) yh_j - (A_i / S_i) sum_j w(i, j) yh_j)
+ *         - (k_i^2 T_i / h) yh_{m_i}
+ *   dx_i = -(g weight / (n p CX_b)) u_i (G_i - xh_i <xh_i, G_i>)
+ *   A row with empty J_i has dx_i = 0 exactly, and so does a row with u_i = 0. mu is data, so dx is the
+ *   gradient of x itself.
+ * Stages and their composition: ast_cx_loss_f32 is ast_cx_center_f32 (when center), ast_cosine_norms_f32
+ * on xc, on yc, ast_cosine_match_f32 with splits 0 (its column outputs go to the workspace, unused),
+ * ast_cx_rowsum_f32 and ast_cx_colmax_f32 with splits 0 and ast_cx_value_f32, bit for bit. The forward
+ * is three passes of 2 m p c FLOP per sample; the backward recomputes D once per group of 512 channels
+ * and multiplies the weight tile once: 2 m p c (ceil(c / 512) + 1) FLOP. Workspaces are device memory,
+ * 256-byte aligned, of at least the matching *_workspace_bytes query. No floating-point atomics, no
+ * host synchronisation, no allocation; a non-finite value stays inside its own sample.
+ * AST_E_NULLPTR: a null pointer. AST_E_SHAPE: a size <= 0 or over the limits above, ns neither n nor 1,
+ * a short workspace. AST_E_UNSUPPORTED: c > AST_CX_MAX_C, splits < 0, h <= 0 or not finite. The queries
+ * return the same negative codes. All checks run before the first launch. */
+#define AST_CX_MAX_C 1024
+#define AST_CX_MAX_PIXELS 16384
+#define AST_CX_EPS 1e-5f
+
+/* mu [ns, c], xc [n, c, m], yc [ns, c, p]: three launches. */
+int ast_cx_center_f32(const float* x, const float* y, float* mu, float* xc, float* yc, int n, int ns, int c,
+                      int m, int p, void* stream);
+
+/* row_sum = S, row_dsum = E [n, m] from the centred maps, their inverse norms and the match's row
+ * minima. splits: the workgroups that share a row's style tiles; 0 is the library's choice, which depends
+ * on the shapes alone. The partials of a row are added in split order, so the result is reproducible for
+ * a given splits; it need not be equal across split counts. Workspace: 8 n splits m bytes and alignment. */
+long long ast_cx_rowsum_workspace_bytes(int n, int ns, int m, int p, int splits);
+int ast_cx_rowsum_f32(const float* xc, const float* yc, const float* inv_x, const float* inv_y,
+                      const float* row_min, float* row_sum, float* row_dsum, int n, int ns, int c, int m, int p,
+                      float h, int splits, void* workspace, long long workspace_bytes, void* stream);
+
+/* col_cx = c_j, col_index = a_j, col_dist = D(a_j, j) [n, p]. The result does not depend on splits, bit
+ * for bit. Workspace: one (value, index, distance) per content tile and style pixel,
+ * 12 n ceil(m / 64) p bytes and alignment. */
+long long ast_cx_colmax_workspace_bytes(int n, int ns, int m, int p);
+int ast_cx_colmax_f32(const float* xc, const float* yc, const float* inv_x, const float* inv_y,
+                      const float* row_min, const float* row_sum, float* col_cx, int* col_index,
+                      float* col_dist, int n, int ns, int c, int m, int p, float h, int splits, void* workspace,
+                      long long workspace_bytes, void* stream);
+
+/* sample_cx [n] = CX_b; *loss += weight / n * sum_b -log CX_b; two launches. */
+int ast_cx_value_f32(const float* col_cx, float* sample_cx, float* loss, int n, int p, float weight,
+                     void* stream);
+
+/* The whole forward; xc, yc (x, y when center == 0), inv_x, inv_y, row_min, row_index, row_sum, row_dsum,
+ * col_index, col_dist and sample_cx are what the backward reads. Workspace: the match's unused column
+ * outputs, 8 n p bytes, and the largest stage workspace. */
+long long ast_cx_loss_workspace_bytes(int n, int ns, int m, int p);
+int ast_cx_loss_f32(const float* x, const float* y, float* mu, float* xc, float* yc, float* inv_x,
+                    float* inv_y, float* row_min, int* row_index, float* row_sum, float* row_dsum,
+                    float* col_cx, int* col_index, float* col_dist, float* sample_cx, float* loss, int n,
+                    int ns, int c, int m, int p, float weight, float h, int center, void* workspace,
+                    long long workspace_bytes, void* stream);
+
+/* dx [n, c, m] from the forward's outputs: the inverse lists, the row scalars, the dense pass and the
+ * finishing pass. Workspace: the lists (4 n (2 m + 1 + p) bytes), the row scalars and flags
+ * (16 n m + 4 n ceil(m / 64)) and G (4 n c m), each aligned. */
+long long ast_cx_loss_backward_workspace_bytes(int n, int c, int m, int p);
+int ast_cx_loss_backward_f32(const float* xc, const float* yc, const float* inv_x, const float* inv_y,
+                             const float* row_min, const int* row_index, const float* row_sum,
+                             const float* row_dsum, const int* col_index, const float* col_dist,
+                             const float* sample_cx, const float* grad_scale, float* dx, int n, int ns, int c,
+                             int m, int p, float weight, float h, void* workspace, long long workspace_bytes,
+                             void* stream);
+
 /* Feature k-means and the label mode filter (csrc/kmeans.hip; an extension, no reference counterpart):
  * the stage that makes the uint8 label maps of the regional transforms above from the features
  * themselves, as Multimodal Style Transfer (Zhang et al., ICCV 2019) clusters the style's relu4_1
