@@ -18,7 +18,8 @@ struct WgCo3Args {
 
 // the q-tile geometry the plan needs (rows of the padded grid x interior columns)
 constexpr int WGCO3_TQH = 4, WGCO3_TQW = 64;
-// partial slots of the border-column pass (after the main kernel's splits; reflect / upsample only)
+// partial slots of the border-column pass (after the main kernel's splits; reflect padding only:
+// zero padding, upsampled or not, leaves the border columns zero)
 constexpr int WGCO3_BORDER_SLOTS = 8;
 
 // true when the MFMA form applies (Cout <= 3, the upsampled width a multiple of 16)

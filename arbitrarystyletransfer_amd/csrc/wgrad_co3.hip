@@ -14,8 +14,9 @@
 //  * the six largest term products, smallest first; a workgroup walks a contiguous range of q tiles
 //    with its accumulators in registers and writes one partial dW (and db) slot, summed in slot
 //    order by the caller (det.h reduce_cols): bitwise reproducible.
-// The two padded border COLUMNS (q x = -1, W; non-zero under reflect / upsample padding) touch only
-// taps kx = 0 and 2 and are a small VALU pass (wgrad_co3_border_kernel) into WGCO3_BORDER_SLOTS more slots.
+// The two padded border COLUMNS (q x = -1, W; non-zero under reflect padding only: zero padding,
+// upsampled or not, leaves them zero) touch only taps kx = 0 and 2 and are a small VALU pass
+// (wgrad_co3_border_kernel) into WGCO3_BORDER_SLOTS more slots.
 // The VALU kernel this replaces (wgrad_smallco_kernel, 27 fp32 FMAs per input value) took 0.83 ms
 // on the config-3 decoder's 8 x 64 x 512^2 -> 3 conv (profiles/r06y_kernel_stats_train.txt).
 #include <hip/hip_runtime.h>
