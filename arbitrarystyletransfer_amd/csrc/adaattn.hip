@@ -22,9 +22,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <algorithm>
 #include "../../include/ast_hip.h"
+#include "env.h"
 #include "wave.h"
 
 namespace {
@@ -777,10 +777,7 @@ struct AttnLayout {  // workspace carve-up (bytes), shared by the size query and
 // bf16 path: split the keys when the query tiles leave the chip underfilled (< 256 workgroups):
 // ~512 workgroups, >= 2 key blocks per split (AST_ATTN_KSPLIT=0: never, for A/B runs)
 void attn_split(int dtype, int n, int nqp, int nkp, int& ksplit, int& kchunk) {
-  static const int on = [] {
-    const char* v = getenv("AST_ATTN_KSPLIT");
-    return v ? atoi(v) : 1;
-  }();
+  static const int on = ast_env::get("AST_ATTN_KSPLIT", 1);
   const int nblk = nkp / BK;
   const bool big = dtype != 0 && (int64_t)n * (nqp / 256) >= 512;  // fp32: 128 queries per workgroup
   const int64_t wgs = (int64_t)n * (nqp / (big ? 256 : 128));

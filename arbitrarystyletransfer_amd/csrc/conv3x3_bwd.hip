@@ -13,11 +13,11 @@
 // each wave 32 x 32 x 9 taps in 9 accumulators. Per 2x32-pixel tile it stages the input halo tile
 // (same source-tile staging as the forward kernel: zero/reflect pad and upsample resolved by the
 // LDS read address, so the 9 taps are constant offsets) and the dY tile; a workgroup sweeps a
-// range of tiles and adds its partial dW with fp32 atomics (the pixel range is split across
-// workgroups). dY may be read from the padded gradient buffer (pitch/plane/offset).
+// range of tiles and writes its partial dW into its own workspace slot (the pixel range is split
+// across workgroups; the slots are summed in order afterwards). dY may be read from the padded
+// gradient buffer (pitch/plane/offset).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "../../include/ast_hip.h"
 #include "conv_common.h"
 #include "x3.h"
@@ -757,149 +757,6 @@ __global__ __launch_bounds__(256) void wgrad_smallco_kernel(WgArgs a) {
   }
 }
 
-// Aligned-shape weight gradient (Cin, Cout multiples of 64; output W a multiple of 32, H even):
-// the same tile, LDS images and MFMA loop as wgrad_kernel, with the staging rebuilt around a
-// register prefetch -- the next tile's input halo (float4 pieces, halo columns as single floats)
-// and dY are loaded while the current tile's MFMAs run, from per-thread offsets computed once.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int UP>
-__global__ __launch_bounds__(256, 2) void wgrad2_kernel(WgArgs a) {
-  using C = WgCfg<UP>;
-  constexpr int SW = C::SW, SR = C::SR, RS = C::RS, PS = C::PS, QV = C::QV, C0 = C::C0;
-  constexpr int NI = WG_CI * SR * QV;        // float4 input pieces per tile
-  constexpr int KI = (NI + 255) / 256;
-  constexpr int NH = WG_CI * SR * 2;         // halo columns per tile
-  constexpr int KH = (NH + 255) / 256;
-  constexpr int KD = WG_CO * WG_PIX / 256;   // dY values per thread (16)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Ps = smem;                   // [WG_CI][PS]
-  float* Ds = smem + WG_CI * PS;      // [WG_PIX][WG_DS]
-  const int Hin = a.Hin, Win = a.Win;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
-  const int wco = wave & 1, wci = wave >> 1;
-  const int co_groups = a.Cout / WG_CO, ci_groups = a.Cin / WG_CI;
-  int b = blockIdx.x;
-  const int cog = b % co_groups;
-  b /= co_groups;
-  const int cig = b % ci_groups;
-  const int split = b / ci_groups;
-  const int co0 = cog * WG_CO, ci0 = cig * WG_CI;
-  const int plane_in = Hin * Win;
-
-  // staging items (recomputed where used, constant divisors): float4 piece e = tid + 256k ->
-  // (channel, halo row, column q); halo item -> (channel, row, left/right)
-#define WG2_ITEM(k)                                                      \
-  const int e_ = min(tid + 256 * (k), NI - 1);                           \
-  const int q_ = e_ % QV, cr_ = e_ / QV, r_ = cr_ % SR, c_ = cr_ / SR;
-#define WG2_HALO(k)                                                      \
-  const int e_ = min(tid + 256 * (k), NH - 1);                           \
-  const int s_ = e_ & 1, cr_ = e_ >> 1, r_ = cr_ % SR, c_ = cr_ / SR;
-  const int d_pix = tid & 63, d_c = tid >> 6;
-  const int d_off = (d_pix / WG_TW) * a.dy_pitch + d_pix % WG_TW;
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = (f32x16){0.f};
-  float bacc = 0.f;
-  int bcol[3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) bcol[kx] = (UP == 1) ? (C0 - 1 + h + kx) : (C0 + ((h + kx - 1) >> 1));
-  const float* prow_base = Ps + (wci * 32 + l32) * PS;
-  const int arow = wco * 32 + l32;
-
-  f32x4 xr[KI];
-  float hr[KH];
-  float dr[KD];
-  auto load_tile = [&](int tile) {
-    int tt = tile;
-    const int tx = tt % a.tiles_x;
-    tt /= a.tiles_x;
-    const int ty = tt % a.tiles_y;
-    const int n = tt / a.tiles_y;
-    const int x0 = tx * WG_TW, y0 = ty * WG_TH;
-    const int sx0 = x0 / UP, sy0 = y0 / UP - 1;
-    const float* xin = a.x + (int64_t)n * a.Cin * plane_in;
-    const int sxl = src_index<UP>(sx0 - 1, Win, a.reflect), sxr = src_index<UP>(sx0 + SW, Win, a.reflect);
-#pragma unroll
-    for (int k = 0; k < KI; ++k) {
-      WG2_ITEM(k)
-      const int sy = src_index<UP>(sy0 + r_, Hin, a.reflect);
-      xr[k] = sy >= 0 ? *reinterpret_cast<const f32x4*>(xin + (ci0 + c_) * plane_in + sy * Win + sx0 + 4 * q_)
-                      : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int k = 0; k < KH; ++k) {
-      WG2_HALO(k)
-      const int sy = src_index<UP>(sy0 + r_, Hin, a.reflect), sx = s_ ? sxr : sxl;
-      hr[k] = (sy >= 0 && sx >= 0) ? xin[(ci0 + c_) * plane_in + sy * Win + sx] : 0.f;
-    }
-    const float* dyn = a.dy + (int64_t)n * a.Cout * a.dy_plane + a.dy_off + (int64_t)y0 * a.dy_pitch + x0 + d_off +
-                       (int64_t)(co0 + d_c) * a.dy_plane;
-#pragma unroll
-    for (int k = 0; k < KD; ++k) dr[k] = dyn[(int64_t)(4 * k) * a.dy_plane];
-  };
-
-  const int t0 = (int)(a.tiles_per_block * split);
-  const int t1 = (int)min(a.ntiles, (int64_t)t0 + a.tiles_per_block);
-  if (t0 < t1) load_tile(t0);
-  for (int tile = t0; tile < t1; ++tile) {
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KI; ++k) {
-      WG2_ITEM(k)
-      float* d = Ps + c_ * PS + r_ * RS + C0 + 4 * q_;
-      d[0] = xr[k][0]; d[1] = xr[k][1]; d[2] = xr[k][2]; d[3] = xr[k][3];
-    }
-#pragma unroll
-    for (int k = 0; k < KH; ++k) {
-      WG2_HALO(k)
-      Ps[c_ * PS + r_ * RS + (s_ ? C0 + SW : C0 - 1)] = hr[k];
-    }
-#pragma unroll
-    for (int k = 0; k < KD; ++k) Ds[d_pix * WG_DS + d_c + 4 * k] = dr[k];
-    __syncthreads();
-    if (tile + 1 < t1) load_tile(tile + 1);
-    if (a.db && cig == 0) {
-      const int c = tid & 63, q = tid >> 6;
-#pragma unroll
-      for (int k = 0; k < WG_PIX / 4; ++k) bacc += Ds[(q * (WG_PIX / 4) + k) * WG_DS + c];
-    }
-#pragma unroll 2
-    for (int kp = 0; kp < WG_PIX / 2; ++kp) {
-      const int prow = (2 * kp) / WG_TW;
-      const int pc0 = (2 * kp) % WG_TW;
-      const float av = Ds[(2 * kp + h) * WG_DS + arow];
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        const int srow = (UP == 1) ? prow + ky : ((prow + ky - 1) >> 1) + 1;
-        const float* rp = prow_base + srow * RS + ((UP == 1) ? pc0 : (pc0 >> 1));
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-          acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, rp[bcol[kx]], acc[ky * 3 + kx], 0, 0, 0);
-      }
-    }
-  }
-  const int ci = ci0 + wci * 32 + l32;
-  float* const dwp = a.dw + (int64_t)split * a.Cout * a.Cin * 9;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      dwp[((int64_t)co * a.Cin + ci) * 9 + t] = acc[t][r];
-    }
-  if (a.db && cig == 0) {  // the 4 quarter-partials of each co, added in quarter order
-    __shared__ float bq[4][64];
-    __syncthreads();
-    bq[tid >> 6][tid & 63] = bacc;
-    __syncthreads();
-    if (tid < 64) a.db[(int64_t)split * a.Cout + co0 + tid] = (bq[0][tid] + bq[1][tid]) + (bq[2][tid] + bq[3][tid]);
-  }
-#undef WG2_ITEM
-#undef WG2_HALO
-}
-
 // Split-bf16 weight gradient (fp32-accurate on the bf16 matrix cores; the x = hi + mid + lo split and
 // the 6-product sum of conv_x3.hip's x3 kernel). dW[co][ci][tap] = sum_pix dY[co][pix] *
 // X[ci][pix + tap] as a GEMM with K = pixels, v_mfma_f32_32x32x16_bf16:
@@ -910,8 +767,8 @@ __global__ __launch_bounds__(256, 2) void wgrad2_kernel(WgArgs a) {
 //    zero/reflect padding and the nearest x2 upsample are all just row addresses, at any alignment.
 // A workgroup (4 waves, 2 x 2 over co x ci) owns 64 co x 64 ci x 9 taps (each wave 32 x 32 x 9 in 9
 // accumulators) and sweeps a range of 2 x 32-pixel tiles; ~80 KB LDS: two workgroups per CU, so
-// one's staging (global loads, split, LDS writes) overlaps the other's MFMAs. Partial dW and db meet
-// through fp32 atomics, as in wgrad2_kernel.
+// one's staging (global loads, split, LDS writes) overlaps the other's MFMAs. Each pixel-range split
+// writes its partial dW and db into its own workspace slot, as in wgrad_kernel.
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
@@ -1092,13 +949,6 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(WgArgs a) {
   }
 }
 
-int g_wgrad_v1 = 0;  // AST_WGRAD_V1=1: always the general kernel (A/B measurements)
-// AST_BWD_ROWPAR=0: the flat elementwise backward kernels (A/B measurements)
-const int g_rowpar = [] {
-  const char* v = getenv("AST_BWD_ROWPAR");
-  return v ? atoi(v) : 1;
-}();
-
 int grid1(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 }  // namespace
 
@@ -1126,7 +976,7 @@ int ast_conv_act_backward_f32(const float* pre, const float* g_pre, const float*
   if (planes <= 0 || h <= 0 || w <= 0) return AST_E_SHAPE;
   const bool al = ((((uintptr_t)pre | (uintptr_t)g_pre | (uintptr_t)g_act | (uintptr_t)dy) & 15) == 0) &&
                   (((uintptr_t)g_pool & 7) == 0);
-  if (g_rowpar && w % 4 == 0 && al && planes * h * (w / 4) < 0x7fffffffLL) {
+  if (w % 4 == 0 && al && planes * h * (w / 4) < 0x7fffffffLL) {
     const unsigned nq = (unsigned)(planes * h * (w / 4));
     hipLaunchKernelGGL(act_backward_v4_kernel, dim3(grid1(nq)), dim3(256), 0, (hipStream_t)stream, pre, g_pre, g_act,
                        g_pool, dy, nq, h, w);
@@ -1148,7 +998,7 @@ int ast_grad_pad_f32(const float* g, const float* mask, float* out_pad, long lon
                      void* stream) {
   if (!g || !out_pad) return AST_E_NULLPTR;
   if (planes <= 0 || h <= 0 || w <= 0 || pitch < w + 2) return AST_E_SHAPE;
-  if (g_rowpar && pitch % 4 == 0 && w % 4 == 0 && ((((uintptr_t)out_pad | (uintptr_t)g | (uintptr_t)mask) & 15) == 0) &&
+  if (pitch % 4 == 0 && w % 4 == 0 && ((((uintptr_t)out_pad | (uintptr_t)g | (uintptr_t)mask) & 15) == 0) &&
       planes * (h + 2) * (pitch / 4) < 0x7fffffffLL) {
     const unsigned nq = (unsigned)(planes * (h + 2) * (pitch / 4));
     hipLaunchKernelGGL(pad_grad_v4_kernel, dim3(grid1(nq)), dim3(256), 0, (hipStream_t)stream, g, mask, out_pad, nq, h,
@@ -1211,7 +1061,7 @@ int ast_pad_up_adjoint_f32(const float* dp_full, float* dx, long long planes, in
   if (planes <= 0 || h_in <= 0 || w_in <= 0) return AST_E_SHAPE;
   if (upsample != 1 && upsample != 2) return AST_E_UNSUPPORTED;
   if (h_in * upsample < 2 || w_in * upsample < 2 || pitch < w_in * upsample + 2) return AST_E_SHAPE;
-  if (g_rowpar && w_in % 4 == 0 && pitch % 4 == 0 && pitch >= w_in * upsample + 4 &&
+  if (w_in % 4 == 0 && pitch % 4 == 0 && pitch >= w_in * upsample + 4 &&
       ((((uintptr_t)dx | (uintptr_t)dp_full) & 15) == 0) && planes * h_in * (w_in / 4) < 0x7fffffffLL) {
     const unsigned nq = (unsigned)(planes * h_in * (w_in / 4));
     if (upsample == 1)
@@ -1239,13 +1089,11 @@ struct WgPlan {
   int64_t ntiles, tiles_per_block, splits;
 };
 
-int g_wgrad_co3 = 1;  // AST_WGRAD_CO3=0: Cout <= 3 on the VALU kernel (A/B measurements)
-
 WgPlan wgrad_plan(int n, int cin, int h_in, int w_in, int cout, int upsample, bool allow_co3 = true) {
   WgPlan p{};
   const int H = h_in * upsample, W = w_in * upsample;
-  p.co3 = allow_co3 && g_wgrad_co3 && !g_wgrad_v1 && wgrad_co3_supported(cin, h_in, w_in, cout, upsample);
-  p.small = !p.co3 && (cout <= 4 || (cout <= 16 && cin <= 16)) && !g_wgrad_v1;
+  p.co3 = allow_co3 && wgrad_co3_supported(cin, h_in, w_in, cout, upsample);
+  p.small = !p.co3 && (cout <= 4 || (cout <= 16 && cin <= 16));
   int64_t target;
   if (p.co3) {  // q tiles: the padded rows x the interior columns; 64 input channels per workgroup
     p.tiles_x = cdiv(W, WGCO3_TQW);
@@ -1271,19 +1119,6 @@ WgPlan wgrad_plan(int n, int cin, int h_in, int w_in, int cout, int upsample, bo
   return p;
 }
 
-void wgrad_env() {
-  static const int v1 = [] {
-    const char* v = getenv("AST_WGRAD_V1");
-    return v ? atoi(v) : 0;
-  }();
-  g_wgrad_v1 = v1;
-  static const int co3 = [] {
-    const char* v = getenv("AST_WGRAD_CO3");
-    return v ? atoi(v) : 1;
-  }();
-  g_wgrad_co3 = co3;
-}
-
 // partial slots a plan needs: its splits, plus the border-column slots of the Cout <= 3 MFMA form
 int64_t wgrad_slots(const WgPlan& p) { return p.splits + (p.co3 ? WGCO3_BORDER_SLOTS : 0); }
 }  // namespace
@@ -1292,7 +1127,6 @@ extern "C" {
 
 long long ast_conv3x3_wgrad_workspace_floats(int n, int cin, int h_in, int w_in, int cout, int upsample) {
   if (n <= 0 || cin <= 0 || h_in <= 0 || w_in <= 0 || cout <= 0 || (upsample != 1 && upsample != 2)) return 0;
-  wgrad_env();
   const WgPlan p = wgrad_plan(n, cin, h_in, w_in, cout, upsample);
   int64_t slots = wgrad_slots(p);
   if (p.co3)  // an unaligned x falls back to the VALU plan (ast_conv3x3_wgrad_ex_f32)
@@ -1317,7 +1151,6 @@ int ast_conv3x3_wgrad_ex_f32(const float* x, const float* dy, float* dw, float* 
   if (dy_pitch < W || dy_plane < (long long)H * dy_pitch || dy_offset < 0) return AST_E_SHAPE;
   if (workspace_floats < ast_conv3x3_wgrad_workspace_floats(n, cin, h_in, w_in, cout, upsample)) return AST_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  wgrad_env();
   // the MFMA form's 16-byte row loads need a 16-byte aligned x
   const WgPlan p = wgrad_plan(n, cin, h_in, w_in, cout, upsample, ((uintptr_t)x & 15) == 0);
   const int64_t wcount = (int64_t)cout * cin * 9;
@@ -1366,12 +1199,8 @@ int ast_conv3x3_wgrad_ex_f32(const float* x, const float* dy, float* dw, float* 
   } else {
     const bool aligned = cin % WG_CI == 0 && cout % WG_CO == 0 && W % WG_TW == 0 && H % WG_TH == 0 && w_in % 4 == 0 &&
                          a.ntiles < 0x7fffffff && (int64_t)n * cin * h_in * w_in < 0x7fffffffLL &&
-                         (int64_t)cout * dy_plane < 0x7fffffffLL && !g_wgrad_v1;
-    static const int wver = [] {
-      const char* v = getenv("AST_WGRAD_VERSION");   // 2 = the fp32 MFMA wgrad2 kernel (A/B measurements)
-      return v ? atoi(v) : 3;
-    }();
-    if (aligned && wver >= 3) {
+                         (int64_t)cout * dy_plane < 0x7fffffffLL;
+    if (aligned) {
       static bool attr = false;
       if (!attr) {
         (void)hipFuncSetAttribute((const void*)wgrad3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1384,11 +1213,7 @@ int ast_conv3x3_wgrad_ex_f32(const float* x, const float* dy, float* dw, float* 
         hipLaunchKernelGGL(wgrad3_kernel<2>, dim3((unsigned)nblk), dim3(256), Wg3Cfg<2>::LDS, s, a);
       else
         hipLaunchKernelGGL(wgrad3_kernel<1>, dim3((unsigned)nblk), dim3(256), Wg3Cfg<1>::LDS, s, a);
-    } else if (aligned && upsample == 2)
-      hipLaunchKernelGGL(wgrad2_kernel<2>, dim3((unsigned)nblk), dim3(256), WgCfg<2>::LDS, s, a);
-    else if (aligned)
-      hipLaunchKernelGGL(wgrad2_kernel<1>, dim3((unsigned)nblk), dim3(256), WgCfg<1>::LDS, s, a);
-    else if (upsample == 2)
+    } else if (upsample == 2)
       hipLaunchKernelGGL(wgrad_kernel<2>, dim3((unsigned)nblk), dim3(256), WgCfg<2>::LDS, s, a);
     else
       hipLaunchKernelGGL(wgrad_kernel<1>, dim3((unsigned)nblk), dim3(256), WgCfg<1>::LDS, s, a);

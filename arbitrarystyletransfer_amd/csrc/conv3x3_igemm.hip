@@ -25,9 +25,9 @@
 // C ABI. The other kernel families are translation units of their own, reached through the launcher
 // declarations of conv_common.h (which lists them) and cin3.h.
 #include <algorithm>
-#include <stdlib.h>
 #include "conv_common.h"
 #include "cin3.h"
+#include "env.h"
 
 namespace {
 
@@ -457,6 +457,15 @@ int auto_config(int cin, int cout, int n, int h, int w, int up, bool pool, bool 
   return tiles >= 256 ? 7 : 1;
 }
 
+// AST_CONV_M16=0|1 (default 1): the split-bf16 tiles on the 32x32x16 MFMA (24-27) | the 16x16x32 one (28-31),
+// for the forward and the dgrad entry alike
+int m16_config(int cfg) {
+  static const int m16 = ast_env::get("AST_CONV_M16", 1);
+  if (cfg >= 24 && cfg <= 27 && m16 == 1) return cfg + 4;
+  if (cfg >= 28 && cfg <= 31 && m16 == 0) return cfg - 4;
+  return cfg;
+}
+
 }  // namespace
 
 extern "C" {
@@ -503,18 +512,7 @@ int ast_conv3x3_fwd_f32_cfg(int cfg, const float* x, const float* x2, int n2, co
   if ((int64_t)round_up(cin, kCinAlign) * 9 * round_up(cout, kCoutAlign) >= ((int64_t)1 << 31)) return AST_E_SHAPE;
   if (cfg < 0) cfg = auto_config(cin, cout, n + n2, H, W, upsample, y_pool != nullptr, in_mean != nullptr);
   if (cfg >= kNumConfigs) return AST_E_UNSUPPORTED;
-  static const int m16 = [] {  // AST_CONV_M16=0|1: the split-bf16 tiles (24-27) on the 32x32x16 | 16x16x32 MFMA
-    const char* v = getenv("AST_CONV_M16");
-    return v ? atoi(v) : 1;
-  }();
-  if (cfg >= 24 && cfg <= 27 && m16 == 1) cfg += 4;
-  if (cfg >= 28 && cfg <= 31 && m16 == 0) cfg -= 4;
-  static const int persist = [] {  // AST_CONV_PERSIST=1: the M16 tiles 28-31 in their persistent form 32-35
-    const char* v = getenv("AST_CONV_PERSIST");
-    return v ? atoi(v) : 0;
-  }();
-  if (cfg >= 28 && cfg <= 31 && persist == 1) cfg += 4;
-  if (cfg >= 28 && cfg <= 31 && persist == 2) cfg += 10;  // AST_CONV_PERSIST=2: 38-41
+  cfg = m16_config(cfg);
   const CfgEntry& e = kConfigs[cfg];
   if (y_pool && (e.rm % 2 != 0 || e.max_cout)) return AST_E_UNSUPPORTED;
   if (e.max_cout && cout > e.max_cout) return AST_E_UNSUPPORTED;
@@ -543,12 +541,7 @@ int ast_conv3x3_dgrad_f32(int cfg, const float* dy, const float* w_tf_packed, fl
   if (cfg < 0) cfg = auto_config(cout, cin, n, h, w, 1, sum2, false);
   // which kernels have the epilogue, and which of them its 2x2-sum form, is the table's dgrad field
   if (cfg >= kNumConfigs || kConfigs[cfg].dgrad < (sum2 ? kDgradSum2 : kDgrad)) return AST_E_UNSUPPORTED;
-  static const int m16 = [] {
-    const char* v = getenv("AST_CONV_M16");
-    return v ? atoi(v) : 1;
-  }();
-  if (cfg >= 24 && cfg <= 27 && m16 == 1) cfg += 4;
-  if (cfg >= 28 && cfg <= 31 && m16 == 0) cfg -= 4;
+  cfg = m16_config(cfg);
 #if !X3_STAGED_EPI
   // the 32x32 kernels' direct-store epilogue (store_tiles) has no input-gradient epilogue: the
   // caller then runs the plain conv and ast_dgrad_finish_f32

@@ -17,8 +17,8 @@
 //    31.5 KiB A tile + 96 KiB = 127.5 KiB, under the 144 KiB of the staged epilogue's regions
 // ------------------------------------------------------------------------------------------------
 #include <algorithm>
-#include <stdlib.h>
 #include "conv_x3.h"
+#include "env.h"
 
 namespace {
 
@@ -367,12 +367,8 @@ int launch_up2c_one(const ConvArgs& a0, const float* w_up2c, hipStream_t s) {
 // The form auto takes (8: 8 waves, one workgroup per CU; 4: 4 waves, one slab buffer, two per CU).
 // AST_UP2C_TILE=8|4 (read once) forces one for A/B runs; the rule is the measured one of DESIGN.md §3.
 int up2c_auto_variant(const ConvArgs& a) {
-  static const int forced = [] {
-    const char* v = getenv("AST_UP2C_TILE");
-    const int t = v ? atoi(v) : 0;
-    return t == 4 || t == 8 ? t : 0;
-  }();
-  if (forced) return forced;
+  static const int forced = ast_env::get("AST_UP2C_TILE", 0);
+  if (forced == 4 || forced == 8) return forced;
   // measured (profiles/r08_up2c_*): a launch whose 8-wave workgroups do not fill the
   // CUs runs on twice as many as 4-wave ones; a full launch gains most where prologue and epilogue
   // weigh most (-18% at 4 chunks per block, -3% at 16 inside the decoder); past 16 nothing is measured

@@ -593,8 +593,8 @@ int launch_x3_one(const ConvArgs& a0, hipStream_t s) {
 // Per block the arithmetic, k order and rounding are conv3x3_x3_kernel<M16>'s: bit-identical.
 // Measured on config 2 (profiles/r04_conv_persistent.txt): 1-2 % SLOWER per dispatch than the
 // one-block-per-workgroup form, also on grids of one block per slot, so the loss is per-block code
-// (argument re-reads, per-block address recomputation), not the static block walk; opt-in only
-// (AST_CONV_PERSIST=1 maps 28-31 to 32-35).
+// (argument re-reads, per-block address recomputation), not the static block walk; reached by config
+// number only (32-35, and 38-41; no automatic choice takes them).
 // It shares this translation unit with conv3x3_x3_kernel on purpose: both call store_region<2>, and
 // the compiler's interprocedural passes look at all of a helper's call sites in the file. Compiled
 // apart, every conv3x3_x3_kernel got a differently scheduled epilogue (same registers; one opt-in

@@ -12,7 +12,6 @@
 //  * Huber: delta = 1, reduction 'mean' (F.huber_loss default).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
 #include "wave.h"
@@ -90,74 +89,12 @@ __device__ __forceinline__ Mom mom_block(Mom m, float* sh) {  // sh: 12 floats
   return r;
 }
 
-// mean and sqrt(M2/(n-1) + eps) of two planes in ONE read of each.
-__device__ void plane_mean_std2(const float* __restrict__ p, const float* __restrict__ q, int64_t n, float eps,
-                                float* sh, float& mp, float& sp, float& mq, float& sq) {
-  float kp = 0.f, kq = 0.f, s1p = 0.f, s2p = 0.f, s1q = 0.f, s2q = 0.f, c = 0.f;
-  const int64_t i0 = threadIdx.x;
-  if (i0 < n) {
-    kp = p[i0];
-    kq = q[i0];
-  }
-  for (int64_t i = i0; i < n; i += kThreads) {
-    const float a = p[i] - kp, b = q[i] - kq;
-    s1p += a;
-    s2p += a * a;
-    s1q += b;
-    s2q += b * b;
-    c += 1.f;
-  }
-  Mom A{c, c > 0.f ? kp + s1p / c : 0.f, c > 0.f ? fmaxf(s2p - s1p * s1p / c, 0.f) : 0.f};
-  Mom B{c, c > 0.f ? kq + s1q / c : 0.f, c > 0.f ? fmaxf(s2q - s1q * s1q / c, 0.f) : 0.f};
-  A = mom_block(A, sh);
-  B = mom_block(B, sh);
-  mp = A.mean;
-  sp = sqrtf(A.m2 / (float)(n - 1) + eps);
-  mq = B.mean;
-  sq = sqrtf(B.m2 / (float)(n - 1) + eps);
-}
-
 // ------------------------------------------------------------------------------------------
 // Content term: w * huber(mvn(x), mvn(y)) (mean over all elements), dx += d/dx.
 // mvn z = (x-mu)/sigma, sigma = sqrt(var_unbiased + 1e-5). With g = dL/dz:
 //   dx = (g - mean(g) - z * sum(g z)/(N-1)) / sigma.
 // ------------------------------------------------------------------------------------------
-// Forward: one read of x and y for both planes' moments, one for the Huber sums. With pstats,
-// also keeps per plane (mu_x, sd_x, mu_y, sd_y, mean(g), sum(g z)/(N-1)) for the backward.
-__global__ __launch_bounds__(kThreads) void mvn_huber_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                             int64_t planes, int64_t hw, float inv_numel, float w,
-                                                             float* loss, float* __restrict__ pstats) {
-  __shared__ float sh[12];
-  float Hs = 0.f;  // this workgroup's planes, in plane order
-  for (int64_t p = blockIdx.x; p < planes; p += gridDim.x) {
-    const float* xp = x + p * hw;
-    const float* yp = y + p * hw;
-    float mx, sx, my, sy;
-    plane_mean_std2(xp, yp, hw, 1e-5f, sh, mx, sx, my, sy);
-    float sh_ = 0.f, sg = 0.f, sgz = 0.f;
-    for (int64_t i = threadIdx.x; i < hw; i += kThreads) {
-      const float z = (xp[i] - mx) / sx;
-      const float d = z - (yp[i] - my) / sy;
-      sh_ += huber(d);
-      const float g = huber_grad(d);
-      sg += g;
-      sgz += g * z;
-    }
-    Hs += block_sum(sh_, sh);
-    if (pstats) {
-      const float G = block_sum(sg, sh);
-      const float GZ = block_sum(sgz, sh);
-      if (threadIdx.x == 0) {
-        float* s = pstats + 6 * p;
-        s[0] = mx; s[1] = sx; s[2] = my; s[3] = sy;
-        s[4] = G / (float)hw;
-        s[5] = GZ / (float)(hw - 1);
-      }
-    }
-  }
-  if (loss) ast_det::loss_acc_commit(loss, w * Hs * inv_numel);
-}
-
+// (the forward is the split-plane form further down: moments_part / mvn_huber_part / mvn_huber_fin)
 // Backward: dx = c * (huber'(d) - mean(g) - z * sum(g z)/(N-1)) / sd_x, one read of x and y.
 // grid (pixel chunks of 4 * kThreads, planes strided by gridDim.y): the plane's statistics are read
 // once, 16-byte accesses where the plane is 4-aligned, no per-element index division.
@@ -363,7 +300,7 @@ __global__ __launch_bounds__(kThreads) void mvn_huber_fin_kernel(const float* __
   if (loss) ast_det::loss_acc_commit(loss, w * t * inv_numel);
 }
 
-// style_stats_kernel's (mu_x, sd_x, mu_y, sd_y) from the chunk partials (unbiased, no eps).
+// The style terms' stats[p] = (mu_x, sd_x, mu_y, sd_y) from the chunk partials (unbiased, no eps).
 __global__ __launch_bounds__(kThreads) void style_stats_fin_kernel(const float* __restrict__ part, int64_t planes,
                                                                    int nchunks, int64_t hw, float* __restrict__ stats) {
   for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < planes; p += (int64_t)gridDim.x * kThreads) {
@@ -456,20 +393,6 @@ __global__ void huber_kernel(const float* __restrict__ x, const float* __restric
 // loss += w*1.25*(mean huber(mu_x-mu_y) + mean huber(sd_x-sd_y)) over the B*C planes;
 // per-plane gradient dx = ra*x + rb with ra = dsd/((N-1) sd), rb = dmu/N - ra*mu.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void style_stats_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                               int64_t hw, float* __restrict__ stats) {
-  __shared__ float sh[12];
-  const int64_t p = blockIdx.x;
-  float mx, sx, my, sy;
-  plane_mean_std2(x + p * hw, y + p * hw, hw, 0.f, sh, mx, sx, my, sy);
-  if (threadIdx.x == 0) {
-    stats[4 * p + 0] = mx;
-    stats[4 * p + 1] = sx;
-    stats[4 * p + 2] = my;
-    stats[4 * p + 3] = sy;
-  }
-}
-
 __global__ void style_moment_loss_kernel(const float* __restrict__ stats, int64_t planes, int64_t hw, float w,
                                          const float* __restrict__ gscale, float* loss, float* __restrict__ ra,
                                          float* __restrict__ rb) {
@@ -542,107 +465,17 @@ __global__ void tv_kernel(const float* __restrict__ x, int64_t planes, int H, in
 // ------------------------------------------------------------------------------------------
 // Gram forward: G[blockIdx.y][b][i][j] = s * sum_{k in split} F[b][i][k] F[b][j][k], k-range split over
 // blockIdx.y (G is the gram itself with one split, else the workspace of partial tiles).
-// 64x64 output tile, 4 waves (2x2 of 32x32), BK = 32; F tiles transposed into LDS [k][row].
+// 64x64 output tile per workgroup; the splits' k chunks are multiples of GBK = 32.
 // G is symmetric: only the tiles ti <= tj are computed (blockIdx.x enumerates
 // them row by row), an off-diagonal tile is stored at (ti, tj) and mirrored at (tj, ti), a diagonal
 // tile's upper half is stored and mirrored (G is exactly symmetric, whatever the summation order).
 // ------------------------------------------------------------------------------------------
 constexpr int GT = 64, GBK = 32;
 
-__global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ F, float* __restrict__ G, int C,
-                                                   int64_t K, int64_t kchunk, float s) {
-  __shared__ float As[GBK][GT + 4];
-  __shared__ float Bs[GBK][GT + 4];
-  const int tiles = (C + GT - 1) / GT;
-  int ti = 0, tj = blockIdx.x;  // upper-triangle index -> (ti, tj), ti <= tj
-  while (tj >= tiles - ti) {
-    tj -= tiles - ti;
-    ++ti;
-  }
-  tj += ti;
-  const int b = blockIdx.z;
-  const int64_t k0 = (int64_t)blockIdx.y * kchunk;
-  const int64_t k1 = min(K, k0 + kchunk);
-  const float* Fb = F + (int64_t)b * C * K;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
-  const int wi = wave & 1, wj = wave >> 1;
-  // a diagonal tile reads its rows once (both operands from As), and its lower-left 32x32 quadrant,
-  // which is never stored (the mirror of the upper-right one), is not computed
-  const bool diag = ti == tj, idle = diag && wi > wj;
-  const float(*Bp)[GT + 4] = diag ? As : Bs;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const bool vec = ((K & 3) == 0) && ((k0 & 3) == 0);
-  // 64 rows x 32 k for each operand: 512 float4 each -> 2 per thread per operand, the next chunk's
-  // in registers while the current one's MFMAs run
-  float4 va[2], vb[2];
-  auto load = [&](int64_t kb) {
-#pragma unroll
-    for (int rep = 0; rep < 2; ++rep) {
-      const int e = tid + rep * 256;  // 0..511
-      const int row = e >> 3, kq = (e & 7) * 4;
-      const int ri = ti * GT + row, rj = tj * GT + row;
-      va[rep] = make_float4(0.f, 0.f, 0.f, 0.f);
-      vb[rep] = va[rep];
-      const int64_t kk = kb + kq;
-      if (vec && kk + 3 < k1) {
-        if (ri < C) va[rep] = *reinterpret_cast<const float4*>(Fb + (int64_t)ri * K + kk);
-        if (!diag && rj < C) vb[rep] = *reinterpret_cast<const float4*>(Fb + (int64_t)rj * K + kk);
-      } else {
-        float ta[4] = {0.f, 0.f, 0.f, 0.f}, tb[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int q = 0; q < 4; ++q) {
-          if (kk + q < k1) {
-            if (ri < C) ta[q] = Fb[(int64_t)ri * K + kk + q];
-            if (!diag && rj < C) tb[q] = Fb[(int64_t)rj * K + kk + q];
-          }
-        }
-        va[rep] = make_float4(ta[0], ta[1], ta[2], ta[3]);
-        vb[rep] = make_float4(tb[0], tb[1], tb[2], tb[3]);
-      }
-    }
-  };
-  if (k0 < k1) load(k0);
-  for (int64_t kb = k0; kb < k1; kb += GBK) {
-#pragma unroll
-    for (int rep = 0; rep < 2; ++rep) {
-      const int e = tid + rep * 256;
-      const int row = e >> 3, kq = (e & 7) * 4;
-      As[kq + 0][row] = va[rep].x; As[kq + 1][row] = va[rep].y; As[kq + 2][row] = va[rep].z; As[kq + 3][row] = va[rep].w;
-      if (!diag) {
-        Bs[kq + 0][row] = vb[rep].x; Bs[kq + 1][row] = vb[rep].y; Bs[kq + 2][row] = vb[rep].z; Bs[kq + 3][row] = vb[rep].w;
-      }
-    }
-    __syncthreads();
-    if (kb + GBK < k1) load(kb + GBK);
-    if (!idle) {
-#pragma unroll
-      for (int kp = 0; kp < GBK / 2; ++kp) {
-        const float a = As[2 * kp + h][wi * 32 + l32];
-        const float bv = Bp[2 * kp + h][wj * 32 + l32];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc, 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  if (idle) return;
-  float* Gb = G + ((int64_t)blockIdx.y * gridDim.z + b) * C * C;
-  const int j = tj * GT + wj * 32 + l32;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int i = ti * GT + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (i < C && j < C && (ti != tj || i <= j)) {  // diagonal tiles: the upper half, mirrored
-      Gb[(int64_t)i * C + j] = s * acc[r];
-      Gb[(int64_t)j * C + i] = s * acc[r];
-    }
-  }
-}
-
-// Gram forward on the split-bf16 matrix cores (round 6; AST_GRAM_X3=0 selects gram_kernel above).
-// Every gram of the style loss is 2 C^2 HW B = 34 GFLOP (C^2 HW is the same at every VGG tap); the
-// LDS-staged gram_kernel runs them at 91-147 TF on the fp32 MFMA, bound by its per-chunk staging
-// and barriers rather than by the MFMA (an LDS-staged split-bf16 form of it was no faster). Here
-// there is no LDS and no barrier in the K loop: the 4 waves of a
+// On the split-bf16 matrix cores (round 6). Every gram of the style loss is 2 C^2 HW B = 34 GFLOP
+// (C^2 HW is the same at every VGG tap); the LDS-staged fp32-MFMA kernel this replaced ran them at
+// 91-147 TF, bound by its per-chunk staging and barriers rather than by the MFMA (an LDS-staged
+// split-bf16 form of it was no faster). Here there is no LDS and no barrier in the K loop: the 4 waves of a
 // workgroup take interleaved 16-k steps of the workgroup's K range, and each computes the whole
 // 64 x 64 tile (2 x 2 blocks of v_mfma_f32_32x32x16_bf16, the six term products). A lane loads its
 // 8 consecutive k of 2 (diagonal tile) or 4 rows straight from HBM, one step ahead, and splits them
@@ -922,11 +755,7 @@ int ast_gram_f32(const float* feat, float* gram, int n, int c, long long hw, flo
     if (!workspace) return AST_E_NULLPTR;
     if (workspace_floats < ast_gram_workspace_floats(n, c, hw)) return AST_E_SHAPE;
   }
-  static const int x3 = [] {  // AST_GRAM_X3=0: the fp32 MFMA gram_kernel (A/B measurements)
-    const char* v = getenv("AST_GRAM_X3");
-    return v ? atoi(v) : 1;
-  }();
-  hipLaunchKernelGGL(x3 ? gram_x3_kernel : gram_kernel, dim3(tiles * (tiles + 1) / 2, (unsigned)splits, n), dim3(256),
+  hipLaunchKernelGGL(gram_x3_kernel, dim3(tiles * (tiles + 1) / 2, (unsigned)splits, n), dim3(256),
                      0, s, feat, splits > 1 ? workspace : gram, c, (int64_t)hw, kchunk, scale);
   if (splits > 1) {
     const int64_t cnt = (int64_t)n * c * c;
@@ -946,16 +775,6 @@ int ast_gram_backward_f32(const float* feat, const float* dgram, float* dfeat, c
   if (nb > 0x7fffffff) return AST_E_SHAPE;
   hipLaunchKernelGGL(gram_bwd_kernel, dim3((unsigned)nb, (c + BI - 1) / BI, n), dim3(256), 0, (hipStream_t)stream,
                      feat, dgram, dfeat, row_a, row_b, c, (int64_t)hw, scale, gscale, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
-}
-
-int ast_mvn_huber_f32(const float* x, const float* y, long long planes, long long hw, float weight, float* loss,
-                      float* pstats, void* stream) {
-  if (!x || !y) return AST_E_NULLPTR;
-  if (planes <= 0 || hw <= 1 || planes > 0x7fffffffLL) return AST_E_SHAPE;
-  const unsigned grid = (unsigned)std::min<long long>(planes, AST_LOSS_SLOTS);
-  hipLaunchKernelGGL(mvn_huber_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, x, y, (int64_t)planes,
-                     (int64_t)hw, (float)(1.0 / ((double)planes * hw)), weight, loss, pstats);
   return (int)hipGetLastError();
 }
 
@@ -1054,18 +873,6 @@ int ast_huber_f32(const float* x, const float* y, long long n, float weight, con
   if (n <= 0) return AST_E_SHAPE;
   hipLaunchKernelGGL(huber_kernel, dim3(loss_grid(n)), dim3(kThreads), 0, (hipStream_t)stream, x, y, (int64_t)n,
                      (float)(1.0 / (double)n), weight, gscale, loss, dx, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
-}
-
-int ast_style_moments_f32(const float* x, const float* y, long long planes, long long hw, float weight,
-                          const float* gscale, float* stats, float* loss, float* row_a, float* row_b, void* stream) {
-  if (!x || !y || !stats) return AST_E_NULLPTR;
-  if ((row_a == nullptr) != (row_b == nullptr)) return AST_E_NULLPTR;
-  if (planes <= 0 || hw <= 0 || planes > 0x7fffffffLL) return AST_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(style_stats_kernel, dim3((unsigned)planes), dim3(kThreads), 0, s, x, y, (int64_t)hw, stats);
-  hipLaunchKernelGGL(style_moment_loss_kernel, dim3(grid_for(planes)), dim3(kThreads), 0, s, stats, (int64_t)planes,
-                     (int64_t)hw, weight, gscale, loss, row_a, row_b);
   return (int)hipGetLastError();
 }
 

@@ -15,8 +15,8 @@
 #include <stdint.h>
 #include "../../include/ast_hip.h"
 #include "det.h"
+#include "env.h"
 #include "wave.h"
-#include "x3.h"
 
 namespace {
 
@@ -325,278 +325,6 @@ __global__ __launch_bounds__(kT) void gemm_reduce_kernel(GemmArgs a, int zper) {
     }
     float* c = a.C + ccol + (int64_t)m * a.sCm;
     *c = a.accumulate ? *c + s : s;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Split-bf16 GEMM (the default for the 1x1 convs): C = A.B with fp32 inputs carried as three bf16
-// terms (x3.h) and the six largest term products, folded into three v_mfma_f32_16x16x32_bf16 per 16
-// channels of K (conv3x3_igemm.hip's M16 scheme) -- fp32-level accuracy at 2.7x the fp32 MFMA rate,
-// so the skinny-K / skinny-MN shapes of a MobileNet block stay HBM-bound.
-// Tile BM (m) x BN (n), 4 waves of (BM/2) x (BN/2), K in chunks of 32. The MFMA's A operand is the
-// N side (B^T rows), its B operand the M side, so a lane's accumulator holds 4 consecutive n of one
-// m: the epilogue writes 16-byte vectors along n (C rows are n-contiguous in every caller).
-// LDS: per side [3 terms][rows][32 + 8] bf16 (80-byte rows: the b128 fragment reads of 16 rows hit
-// distinct banks). Staging: a thread owns (row, 8 consecutive k) items -- two 16-byte loads when k
-// is contiguous, else eight loads coalesced across the lanes' consecutive rows -- splits them and
-// writes one 16-byte vector per term; the next chunk's loads are in flight during the MFMAs.
-// Folded K (foldK = P) needs P % 8 == 0 so that 8 consecutive k stay in one image (host-checked).
-// ------------------------------------------------------------------------------------------------
-constexpr int X3KC = 32, X3KP = X3KC + 8;
-
-struct X3Flags {
-  int vecA, vecB, vecC, vecP;  // 16-byte paths legal: A / B k-runs, C / partial-tile n-runs
-  int ntn;                     // n-tiles; a workgroup walks n-tiles blockIdx.x, + gridDim.x, ...
-};
-
-// Staging map of one operand side with R rows: item it -> (row, 8-k group). When k is the
-// contiguous dimension, 4 consecutive lanes take the 4 groups of one row (128-byte runs per row);
-// otherwise consecutive lanes take consecutive rows (every k load coalesced across the lanes).
-template <int R>
-__device__ __forceinline__ void x3_item(int it, bool kfast, int& row, int& kg) {
-  if (kfast) {
-    row = it >> 2;
-    kg = it & 3;
-  } else {
-    row = it % R;
-    kg = it / R;
-  }
-}
-
-template <int BM, int BN>
-__global__ __launch_bounds__(kT, 2) void gemm_x3_kernel(GemmArgs a, X3Flags f) {
-  using ast_x3::bf16;
-  using ast_x3::bf16x8;
-  using ast_x3::f32x4;
-  __shared__ __attribute__((aligned(16))) bf16 Ns[3][BN][X3KP];
-  __shared__ __attribute__((aligned(16))) bf16 Ms[3][BM][X3KP];
-  constexpr int WN = BN / 2, WM = BM / 2, TN = WN / 16, TM = WM / 16;
-  constexpr int NI = BN * 4 / kT, MI = BM * 4 / kT;  // staging items per thread
-  static_assert(NI >= 1 && MI >= 1 && BN * 4 % kT == 0 && BM * 4 % kT == 0, "tile");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave & 1, wm = wave >> 1;
-  const int m0 = blockIdx.y * BM;
-  const int b = blockIdx.z / a.ksplit, ks = blockIdx.z % a.ksplit;
-  const int kbeg = ks * a.kchunk, kend = min(a.K, kbeg + a.kchunk);
-  if ((int)blockIdx.x >= f.ntn) return;  // (an empty K split still stores its zero tiles)
-  const bool kfA = a.sAk == 1, kfB = a.sBk == 1;
-  const float* A = a.A + b * a.sAb;
-  const float* B = a.B + b * a.sBb;
-  // k offsets: folded K walks images through the batch stride (batch == 1 then)
-  auto koffA = [&](int k) -> int64_t {
-    if (a.foldK) {
-      const int bb = k / a.foldK;
-      return bb * a.sAb + (int64_t)(k - bb * a.foldK) * a.sAk;
-    }
-    return (int64_t)k * a.sAk;
-  };
-  auto koffB = [&](int k) -> int64_t {
-    if (a.foldK) {
-      const int bb = k / a.foldK;
-      return bb * a.sBb + (int64_t)(k - bb * a.foldK) * a.sBk;
-    }
-    return (int64_t)k * a.sBk;
-  };
-  int64_t noff[NI], moff[MI];
-  bool nok[NI], mok[MI];
-  auto set_ntile = [&](int t) {  // per-item column offsets of n-tile t
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      int row, kg;
-      x3_item<BN>(tid + i * kT, kfB, row, kg);
-      const int n = t * BN + row;
-      nok[i] = n < a.N;
-      if (a.foldN) {
-        const int bb = n / a.foldN;
-        noff[i] = bb * a.sBb + (int64_t)(n - bb * a.foldN) * a.sBn;
-      } else {
-        noff[i] = (int64_t)n * a.sBn;
-      }
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    int row, kg;
-    x3_item<BM>(tid + i * kT, kfA, row, kg);
-    const int m = m0 + row;
-    mok[i] = m < a.M;
-    moff[i] = (int64_t)m * a.sAm;
-  }
-  float rn[NI][8], rm[MI][8];
-  auto load8 = [&](const float* base, bool ok, int kf, int64_t sK, bool vec, float* v) {
-    if (ok && vec && kf + 8 <= kend) {
-      const f32x4 u0 = *(const f32x4*)base, u1 = *(const f32x4*)(base + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = u0[j];
-        v[4 + j] = u1[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (ok && kf + j < kend) ? base[j * sK] : 0.f;
-    }
-  };
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      int row, kg;
-      x3_item<BN>(tid + i * kT, kfB, row, kg);
-      const int kf = k0 + 8 * kg;
-      const float* p = B + noff[i] + (kf < kend ? koffB(kf) : 0);
-      load8(p, nok[i], kf, a.sBk, f.vecB, rn[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      int row, kg;
-      x3_item<BM>(tid + i * kT, kfA, row, kg);
-      const int kf = k0 + 8 * kg;
-      const float* p = A + moff[i] + (kf < kend ? koffA(kf) : 0);
-      load8(p, mok[i], kf, a.sAk, f.vecA, rm[i]);
-    }
-  };
-  auto split_store = [&](const float* v, bf16* d0, bf16* d1, bf16* d2) {
-    bf16x8 t0, t1, t2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      bf16 h, md, l;
-      ast_x3::split3(v[j], h, md, l);
-      t0[j] = h;
-      t1[j] = md;
-      t2[j] = l;
-    }
-    *(bf16x8*)d0 = t0;
-    *(bf16x8*)d1 = t1;
-    *(bf16x8*)d2 = t2;
-  };
-  auto stage = [&]() {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      int row, kg;
-      x3_item<BN>(tid + i * kT, kfB, row, kg);
-      split_store(rn[i], &Ns[0][row][8 * kg], &Ns[1][row][8 * kg], &Ns[2][row][8 * kg]);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      int row, kg;
-      x3_item<BM>(tid + i * kT, kfA, row, kg);
-      split_store(rm[i], &Ms[0][row][8 * kg], &Ms[1][row][8 * kg], &Ms[2][row][8 * kg]);
-    }
-  };
-  f32x4 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int g = lane >> 4, r16 = lane & 15;
-  const bool first = g < 2;
-  // epilogue of n-tile t: lane holds D[n = 4 (lane >> 4) + r][m = lane & 15] of each 16 x 16 tile
-  auto epilogue = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < TN; ++i) {
-      const int n = t * BN + wn * WN + i * 16 + 4 * g;
-      if (n >= a.N) continue;
-      const bool full = n + 3 < a.N;
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        const int m = m0 + wm * WM + j * 16 + r16;
-        if (m >= a.M) continue;
-        const f32x4 v = acc[i][j];
-        if (a.part) {
-          float* P = a.part + ((int64_t)blockIdx.z * a.M + m) * a.N + n;
-          if (full && f.vecP) {
-            *(f32x4*)P = v;
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (n + r < a.N) P[r] = v[r];
-          }
-          continue;
-        }
-        if (full && f.vecC) {  // 4 consecutive n in one image, n-contiguous and aligned (host-checked)
-          int64_t ccol;
-          if (a.foldN) {
-            const int bb = n / a.foldN;
-            ccol = bb * a.sCb + (int64_t)(n - bb * a.foldN);
-          } else {
-            ccol = b * a.sCb + n;
-          }
-          f32x4* c = (f32x4*)(a.C + ccol + (int64_t)m * a.sCm);
-          *c = a.accumulate ? *c + v : v;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int nn = n + r;
-            if (nn >= a.N) break;
-            int64_t ccol;
-            if (a.foldN) {
-              const int bb = nn / a.foldN;
-              ccol = bb * a.sCb + (int64_t)(nn - bb * a.foldN) * a.sCn;
-            } else {
-              ccol = b * a.sCb + (int64_t)nn * a.sCn;
-            }
-            float* c = a.C + ccol + (int64_t)m * a.sCm;
-            *c = a.accumulate ? *c + v[r] : v[r];
-          }
-        }
-      }
-    }
-  };
-  // (n-tile, K chunk) pairs in one pipelined walk: the next pair's loads (the next tile's first
-  // chunk after a tile's last) are in flight during this pair's MFMAs and the tile's epilogue
-  int t = blockIdx.x, k0 = kbeg;
-  set_ntile(t);
-  load(k0);
-  for (;;) {
-    __syncthreads();  // the previous chunk's fragments are read
-    stage();
-    __syncthreads();
-    int nt = t, nk = k0 + X3KC;
-    if (nk >= kend) {
-      nt = t + gridDim.x;
-      nk = kbeg;
-    }
-    const bool more = nt < f.ntn;
-    if (more) {
-      if (nt != t) set_ntile(nt);
-      load(nk);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int ko = s * 16 + 8 * (g & 1);
-      bf16x8 f1[TN], f2[TN], g1[TM], g2[TM], g3[TM];
-#pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const int row = wn * WN + i * 16 + r16;
-        f1[i] = *(const bf16x8*)&Ns[first ? 0 : 1][row][ko];
-        f2[i] = *(const bf16x8*)&Ns[first ? 0 : 2][row][ko];
-      }
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        const int row = wm * WM + j * 16 + r16;
-        g1[j] = *(const bf16x8*)&Ms[0][row][ko];
-        g2[j] = *(const bf16x8*)&Ms[first ? 1 : 0][row][ko];
-        g3[j] = *(const bf16x8*)&Ms[first ? 2 : 1][row][ko];
-      }
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          f32x4 c = acc[i][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1[i], g3[j], c, 0, 0, 0);  // n_hi m_lo + n_mid m_mid
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2[i], g2[j], c, 0, 0, 0);  // n_hi m_mid + n_lo m_hi
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1[i], g1[j], c, 0, 0, 0);  // n_hi m_hi + n_mid m_hi
-        }
-    }
-    if (k0 + X3KC >= kend) {  // the tile's last chunk: store and restart the accumulators
-      epilogue(t);
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    if (!more) break;
-    t = nt;
-    k0 = nk;
   }
 }
 
@@ -1102,52 +830,23 @@ int ast_mbt_gemm_f32(const float* A, const float* B, float* C, int M, int N, int
              ksplit, 0, accumulate, foldK, foldN, 0, 0};
   a.kchunk = ((K + ksplit - 1) / ksplit + GK - 1) / GK * GK;
   {  // float4 k-runs: K, the chunk and the folded image stride multiples of 4, 16-byte aligned rows
-    static const int vec = [] {  // AST_MBGEMM_VEC=0: scalar staging (A/B runs)
-      const char* v = getenv("AST_MBGEMM_VEC");
-      return v ? atoi(v) : 1;
-    }();
+    static const int vec = ast_env::get("AST_MBGEMM_VEC", 1);  // 0: scalar staging (A/B runs)
     const bool kok = vec && K % 4 == 0 && a.kchunk % 4 == 0 && (foldK == 0 || foldK % 4 == 0);
     a.vecA = kok && sAk == 1 && sAm % 4 == 0 && sAb % 4 == 0 && ((uintptr_t)A & 15) == 0;
     a.vecB = kok && sBk == 1 && sBn != 1 && sBn % 4 == 0 && sBb % 4 == 0 && ((uintptr_t)B & 15) == 0;
   }
   hipStream_t st = (hipStream_t)stream;
-  // AST_MBGEMM_X3=1: the split-bf16 kernel (fp32-level accuracy, repeatable; measured 3% slower
-  // on the AST step than the fp32-MFMA kernel, whose skinny-K shapes are latency-, not MFMA-bound)
-  static const int x3 = [] {
-    const char* v = getenv("AST_MBGEMM_X3");
-    return v ? atoi(v) : 0;
-  }();
   const dim3 grid((unsigned)((N + GT - 1) / GT), (unsigned)((M + GT - 1) / GT), (unsigned)(batch * ksplit));
-  static const int wide = [] {  // AST_MBGEMM_WIDE=0: gemm_kernel for these shapes too (A/B measurements)
-    const char* v = getenv("AST_MBGEMM_WIDE");
-    return v ? atoi(v) : 1;
-  }();
   {
     const int P = foldN ? foldN : N;
-    if (wide && !x3 && batch == 1 && ksplit == 1 && !foldK && sBn == 1 && sCn == 1 && need == 0 && P % 4 == 0 &&
+    if (batch == 1 && ksplit == 1 && !foldK && sBn == 1 && sCn == 1 && need == 0 && P % 4 == 0 &&
         N % 4 == 0 && sBk % 4 == 0 && (foldN == 0 || sBb % 4 == 0) && ((uintptr_t)B & 15) == 0) {
       const dim3 g((unsigned)((N + WGN - 1) / WGN), (unsigned)((M + GT - 1) / GT));
       hipLaunchKernelGGL(gemm_wide_kernel, g, dim3(kT), 0, st, a, P);
       return (int)hipGetLastError();
     }
   }
-  if (x3 && (foldK == 0 || foldK % 8 == 0)) {  // split-bf16 path (8 consecutive k stay in one image)
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    X3Flags fl{};
-    fl.vecA = sAk == 1 && al(A) && sAm % 4 == 0 && (sAb % 4 == 0 || (batch == 1 && !foldK));
-    fl.vecB = sBk == 1 && al(B) && sBn % 4 == 0 && (sBb % 4 == 0 || (batch == 1 && !foldK && !foldN));
-    fl.vecC = sCn == 1 && al(C) && sCm % 4 == 0 && (sCb % 4 == 0 || (batch == 1 && !foldN)) &&
-              (foldN ? foldN % 4 == 0 : true);
-    fl.vecP = N % 4 == 0 && (need == 0 || al(workspace));
-    // n-tiles walked by a grid of ~2 resident workgroups per CU (pipelined across tiles)
-    fl.ntn = (N + 127) / 128;
-    const int mt = (M + 63) / 64, zb = batch * ksplit;
-    const int want = (int)((512 + (int64_t)mt * zb - 1) / ((int64_t)mt * zb));
-    const dim3 gx((unsigned)(want < fl.ntn ? want : fl.ntn), (unsigned)mt, (unsigned)zb);
-    hipLaunchKernelGGL((gemm_x3_kernel<64, 128>), gx, dim3(kT), 0, st, a, fl);
-  } else {
-    hipLaunchKernelGGL(gemm_kernel, grid, dim3(kT), 0, st, a);
-  }
+  hipLaunchKernelGGL(gemm_kernel, grid, dim3(kT), 0, st, a);
   if (need > 0) {  // the partial tiles, summed in (image, split) order
     const bool shared = sCb == 0 && batch > 1;
     const int cimgs = shared ? 1 : batch;

@@ -20,8 +20,8 @@
 // Storage type T is float or __bf16; all arithmetic and accumulation is fp32.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "../../include/ast_hip.h"
+#include "env.h"
 #include "mb_common.h"
 #include "det.h"
 #include "wave.h"
@@ -1535,17 +1535,9 @@ int launch_ed_th(EdArgs a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int g_ed_th = 0;  // AST_MB_ED_TH=16|4|2 sets the v1 tile height (A/B measurements)
-
 template <typename T, int K, int S, int UP, bool EXPAND>
 int launch_ed(EdArgs a, hipStream_t st) {
   constexpr int TW = S == 1 ? 32 : 16;  // output tile width; 8/4/2 rows as LDS allows
-  if (g_ed_th == 16 && ed_lds_bytes<T, K, S, 16, TW>(a.cin_pad, EXPAND) <= kLdsBudgetMax)
-    return launch_ed_th<T, K, S, UP, EXPAND, 16, TW>(a, st);
-  if (g_ed_th == 4 && ed_lds_bytes<T, K, S, 4, TW>(a.cin_pad, EXPAND) <= kLdsBudget)
-    return launch_ed_th<T, K, S, UP, EXPAND, 4, TW>(a, st);
-  if (g_ed_th == 2 && ed_lds_bytes<T, K, S, 2, TW>(a.cin_pad, EXPAND) <= kLdsBudget)
-    return launch_ed_th<T, K, S, UP, EXPAND, 2, TW>(a, st);
   if (ed_lds_bytes<T, K, S, 8, TW>(a.cin_pad, EXPAND) <= kLdsBudget)
     return launch_ed_th<T, K, S, UP, EXPAND, 8, TW>(a, st);
   if (ed_lds_bytes<T, K, S, 4, TW>(a.cin_pad, EXPAND) <= kLdsBudget)
@@ -1556,8 +1548,6 @@ int launch_ed(EdArgs a, hipStream_t st) {
     return launch_ed_th<T, K, S, UP, EXPAND, 2, 16>(a, st);
   return AST_E_UNSUPPORTED;
 }
-
-int g_ed_big = 1;  // AST_MB_ED_BIG=0 disables the 16-wave tile (A/B measurements)
 
 template <int K, int UP, bool EXPAND, int TH, int TW, int R, int NT = 512>
 int launch_ed2(EdArgs a, hipStream_t st) {
@@ -1580,16 +1570,12 @@ int launch_ed2_auto(EdArgs a, hipStream_t st) {
   if (EXPAND && a.cin_pad > 256) return AST_E_UNSUPPORTED;
   const int h = a.hid;
   if (ed2_lds_bytes<K, 8, 32, 2>(a.cin_pad, EXPAND, h) <= kLdsBudget) return launch_ed2<K, UP, EXPAND, 8, 32, 2>(a, st);
-  if (g_ed_big && ed2_lds_bytes<K, 8, 32, 1, 1024>(a.cin_pad, EXPAND, h) <= kLdsBudgetMax)  // 16 waves, 1 WG/CU
+  if (ed2_lds_bytes<K, 8, 32, 1, 1024>(a.cin_pad, EXPAND, h) <= kLdsBudgetMax)  // 16 waves, 1 WG/CU
     return launch_ed2<K, UP, EXPAND, 8, 32, 1, 1024>(a, st);
   if (ed2_lds_bytes<K, 4, 32, 1>(a.cin_pad, EXPAND, h) <= kLdsBudget) return launch_ed2<K, UP, EXPAND, 4, 32, 1>(a, st);
   if (ed2_lds_bytes<K, 4, 32, 1>(a.cin_pad, EXPAND, h) <= kLdsBudgetMax) return launch_ed2<K, UP, EXPAND, 4, 32, 1>(a, st);
   return AST_E_UNSUPPORTED;
 }
-
-int g_ed_version = 4;  // AST_MB_ED=1|2|3 select the v1|v2|v3 kernels (A/B measurements); 4: v4 where it applies
-
-int g_ed3_nt = 0;  // AST_MB_ED3_NT=512|1024 forces the v3 workgroup size (A/B measurements)
 
 template <int K>
 int launch_ed3(EdArgs a, hipStream_t st) {
@@ -1604,28 +1590,28 @@ int launch_ed3(EdArgs a, hipStream_t st) {
   if (ed_plan(a, (int64_t)a.tiles_x * a.tiles_y)) return 0;
   // two 8-wave workgroups per CU when the LDS allows, else one 16-wave workgroup (latency hiding)
   const bool two = lds <= kLdsBudget;
-  const int nt = g_ed3_nt ? g_ed3_nt : two ? 512 : 1024;
-  auto kern = nt == 512 ? (two ? expand_dw3_kernel<K, 512, 2> : expand_dw3_kernel<K, 512, 1>)
-                        : expand_dw3_kernel<K, 1024, 1>;
+  const int nt = two ? 512 : 1024;
+  auto kern = two ? expand_dw3_kernel<K, 512, 2> : expand_dw3_kernel<K, 1024, 1>;
   const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(nt), lds, st, a);
   return (int)hipGetLastError();
 }
 
+// ver: AST_MB_ED, 4 unless set; 1|2|3 stop at the v1|v2|v3 kernels (tests/test_gpu_mb_stages.py forces each)
 template <typename T>
-int dispatch_ed(EdArgs a, int k, int s, int up, bool expand, hipStream_t st) {
-  if (sizeof(T) == 2 && (up == 1 || !expand) && g_ed_version >= 4 && a.c1 == a.cin &&
+int dispatch_ed(EdArgs a, int k, int s, int up, bool expand, int ver, hipStream_t st) {
+  if (sizeof(T) == 2 && (up == 1 || !expand) && ver >= 4 && a.c1 == a.cin &&
       (int64_t)a.cin_pad * 2 * a.h * a.w < 0x7fffffffLL) {
     const int r = ast_mb::launch_ed4(a, k, s, st);
     if (r != AST_E_UNSUPPORTED || a.nod) return r;
   }
   if (a.nod) return AST_E_UNSUPPORTED;  // pool-only: the v4 kernels only
-  if (sizeof(T) == 2 && s == 1 && up == 1 && expand && g_ed_version >= 3) {
+  if (sizeof(T) == 2 && s == 1 && up == 1 && expand && ver >= 3) {
     const int r = k == 3 ? launch_ed3<3>(a, st) : k == 5 ? launch_ed3<5>(a, st) : AST_E_UNSUPPORTED;
     if (r != AST_E_UNSUPPORTED) return r;
   }
-  if (sizeof(T) == 2 && s == 1 && g_ed_version >= 2) {
+  if (sizeof(T) == 2 && s == 1 && ver >= 2) {
     int r = AST_E_UNSUPPORTED;
     if (expand && up == 1 && k == 3) r = launch_ed2_auto<3, 1, true>(a, st);
     // k5 with narrow inputs: v2 only has the 4-row tile here (the 8-row one exceeds 80 KB of LDS),
@@ -1716,26 +1702,6 @@ int ed_setup(int dtype, const void* x1, const void* x2, int c1, int n, int cin, 
     return AST_E_SHAPE;
   }
   if (dtype != 0 && dtype != 1) return AST_E_UNSUPPORTED;
-  static const int ver = [] {
-    const char* v = getenv("AST_MB_ED");
-    return v ? atoi(v) : 4;
-  }();
-  g_ed_version = ver;
-  static const int big = [] {
-    const char* v = getenv("AST_MB_ED_BIG");
-    return v ? atoi(v) : 1;
-  }();
-  g_ed_big = big;
-  static const int th = [] {
-    const char* v = getenv("AST_MB_ED_TH");
-    return v ? atoi(v) : 0;
-  }();
-  g_ed_th = th;
-  static const int ed3_nt = [] {
-    const char* v = getenv("AST_MB_ED3_NT");
-    return v ? atoi(v) : 0;
-  }();
-  g_ed3_nt = ed3_nt;
   *out = EdArgs{x1, x2, c1, n, cin, h, w, h * up, w * up, ho, wo, w1p, nullptr, hid, expand ? cin_pad : 0,
                 nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
   return 0;
@@ -1743,8 +1709,9 @@ int ed_setup(int dtype, const void* x1, const void* x2, int c1, int n, int cin, 
 
 int ed_dispatch(int dtype, EdArgs a, int k, int stride, int up, hipStream_t st) {
   const bool expand = a.w1 != nullptr;
-  if (dtype == 0) return dispatch_ed<float>(a, k, stride, up, expand, st);
-  return dispatch_ed<bf16>(a, k, stride, up, expand, st);
+  static const int ver = ast_env::get("AST_MB_ED", 4);
+  if (dtype == 0) return dispatch_ed<float>(a, k, stride, up, expand, ver, st);
+  return dispatch_ed<bf16>(a, k, stride, up, expand, ver, st);
 }
 }  // namespace
 

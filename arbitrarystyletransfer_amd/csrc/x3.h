@@ -1,7 +1,7 @@
 // Split-bf16 ("x3") helpers shared by the fp32-accurate MFMA kernels: an fp32 value is carried as
 // three bf16 terms x = hi + mid + lo (exact for finite x), and a product as the six largest term
 // products, folded into three v_mfma_f32_16x16x32_bf16 per 16 channels of K (see conv_x3.hip
-// M16 and mbtrain.hip gemm_x3_kernel).
+// M16 and conv3x3_bwd.hip wgrad3_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 

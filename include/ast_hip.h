@@ -884,7 +884,7 @@ int ast_gram_f32(const float* feat, float* gram, int n, int c, long long hw, flo
 
 /* dfeat[b] (+)= scale * (dgram[b] + dgram[b]^T) feat[b] + row_a[b,i] * feat[b,i,:] + row_b[b,i]
  * (the backward of gram_matrix, with compute_style_loss's mean/std gradients fused: row_a/row_b
- * from ast_style_moments_f32, or both NULL). */
+ * from ast_style_moments_ws_f32, or both NULL). */
 int ast_gram_backward_f32(const float* feat, const float* dgram, float* dfeat,
                           const float* row_a, const float* row_b,
                           int n, int c, long long hw, float scale, const float* gscale,
@@ -892,13 +892,10 @@ int ast_gram_backward_f32(const float* feat, const float* dgram, float* dfeat,
 
 /* compute_content_loss(mean_variance_norm(x), mean_variance_norm(y)) (losses.py:124-126,
  * models.py:64-68; train.py:225): loss += weight * mean(huber(mvn(x) - mvn(y))). With pstats
- * [planes, 6] (or NULL) it also keeps what the backward needs. */
-int ast_mvn_huber_f32(const float* x, const float* y, long long planes, long long hw, float weight,
-                      float* loss, float* pstats, void* stream);
-
-/* The same, split over (chunk, plane) workgroups: partial moments and Huber sums of each chunk of
- * 8192 elements go to `workspace` (ast_plane_stats_workspace_floats(planes, hw) floats) and are
- * merged in chunk order, so few large planes fill the chip. Three launches; same outputs. */
+ * [planes, 6] (or NULL) it also keeps what the backward needs.
+ * Split over (chunk, plane) workgroups: partial moments and Huber sums of each chunk of 8192
+ * elements go to `workspace` (ast_plane_stats_workspace_floats(planes, hw) floats) and are merged
+ * in chunk order, so few large planes fill the chip. Three launches. */
 long long ast_plane_stats_workspace_floats(long long planes, long long hw);
 int ast_mvn_huber_ws_f32(const float* x, const float* y, long long planes, long long hw, float weight,
                          float* loss, float* pstats, float* workspace, long long workspace_floats,
@@ -916,13 +913,9 @@ int ast_huber_f32(const float* x, const float* y, long long n, float weight, con
 /* Mean/std part of compute_style_loss (losses.py:130-134):
  * loss += weight * 1.25 * (mean huber(mu_x - mu_y) + mean huber(sd_x - sd_y)) over planes,
  * stats [planes, 4] = (mu_x, sd_x, mu_y, sd_y); row_a/row_b [planes] = per-plane gradient
- * d/dx = row_a * x + row_b (NULL: value only). */
-int ast_style_moments_f32(const float* x, const float* y, long long planes, long long hw, float weight,
-                          const float* gscale, float* stats, float* loss, float* row_a, float* row_b,
-                          void* stream);
-
-/* The same with the plane moments split over (chunk, plane) workgroups through `workspace`
- * (ast_plane_stats_workspace_floats(planes, hw) floats; merged in chunk order). */
+ * d/dx = row_a * x + row_b (NULL: value only). The plane moments are split over (chunk, plane)
+ * workgroups through `workspace` (ast_plane_stats_workspace_floats(planes, hw) floats; merged in
+ * chunk order). */
 int ast_style_moments_ws_f32(const float* x, const float* y, long long planes, long long hw, float weight,
                              const float* gscale, float* stats, float* loss, float* row_a, float* row_b,
                              float* workspace, long long workspace_floats, void* stream);

@@ -9,6 +9,8 @@ cin <= 4) and 42, 43 (cin <= 3 MFMA) without it only; everything else refused, 3
 this shape the swapped conv reads 16 channels (one K chunk: the smallest the split-bf16 tiles take),
 so 18-23, 42 and 43 refuse it in their launchers as well, and the set is 24-35 both times
 (test_gpu_parity.py::test_conv3x3_cin3_dgrad_epilogue launches 42 and 43 on a 3-channel gradient).
+With AST_CONV_M16 unset (its default, 1) the entry runs an offered 24-27 as 28-31, the same tiles on the
+16x16x32 MFMA, so those four indices are launched twice over.
 
 Tolerance: rel_inf <= 5e-5, the bar of tests/test_gpu_dgrad_fused.py, against
 functional.conv_input_grad_same (and its 2x2 window sum for upsample 2)."""

@@ -98,7 +98,7 @@ DEC_CASES = [
     (1, 16, 9, 13, 16, 2, True),
     (1, 4, 2, 2, 64, 1, True),      # smallest reflect-padded map
     (1, 12, 1, 3, 64, 2, True),     # upsampled 1-row map
-    # aligned shapes (Cin, Cout % 64 == 0, W % 32 == 0): the prefetching wgrad2 kernel
+    # aligned shapes (Cin, Cout % 64 == 0, W % 32 == 0): the split-bf16 wgrad3 kernel
     (2, 64, 6, 32, 64, 1, True),
     (1, 128, 4, 16, 64, 2, True),
     (1, 64, 2, 64, 128, 1, False),
