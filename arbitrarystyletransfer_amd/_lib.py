@@ -214,6 +214,13 @@ SIGNATURES = {
     "ast_color_convert_backward_f32": (_i, [_p, _p, _p, _i, _ll, _i, _p]),
     "ast_luma_transfer_f32": (_i, [_p, _p, _p, _i, _ll, _p]),
     "ast_luma_transfer_bf16": (_i, [_p, _p, _p, _i, _ll, _p]),
+    "ast_moment_stats_workspace_bytes": (_ll, [_i, _i, _ll, _i]),
+    "ast_moment_stats_f32": (_i, [_p, _p, _p, _i, _i, _ll, _i, _p, _ll, _p]),
+    "ast_moment_loss_workspace_bytes": (_ll, [_i, _i, _ll, _i]),
+    "ast_moment_loss_f32": (_i, [_p] * 8 + [_i, _i, _i, _ll, _f, _i, _p, _ll, _p]),
+    "ast_moment_loss_backward_f32": (_i, [_p] * 6 + [_i, _i, _ll, _f, _i, _p]),
+    "ast_resize_bilinear_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _f, _p]),
+    "ast_resize_bilinear_adjoint_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 ERRORS = {-1: "null pointer", -2: "bad shape", -3: "unsupported configuration"}

@@ -439,6 +439,45 @@ def color_convert(x, mode):
     return ops.color_convert(x, mode)
 
 
+class ResizeBilinearFn(torch.autograd.Function):
+    """ops.resize_bilinear(x, size, add, sign) with the HIP adjoint as its backward:
+    d x = sign * R^T g (one launch), d add = g."""
+
+    @staticmethod
+    def forward(ctx, x, size, add=None, sign=1.0):
+        ctx.in_size = tuple(x.shape[-2:])
+        ctx.sign = float(sign) if add is not None else 1.0
+        ctx.has_add = add is not None
+        return ops.resize_bilinear(x, size, add=add, sign=sign)
+
+    @staticmethod
+    def backward(ctx, g):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.resize_bilinear_adjoint(g, ctx.in_size)
+            if ctx.sign != 1.0:
+                dx = dx.mul_(ctx.sign)
+        return dx, None, g if ctx.has_add and ctx.needs_input_grad[2] else None, None
+
+
+class LapCollapseFn(torch.autograd.Function):
+    """ops.lap_collapse(levels) with autograd into every level: level 0 receives g, level l + 1 the
+    adjoint of level l's gradient through the resize between them, one adjoint launch per level."""
+
+    @staticmethod
+    def forward(ctx, *levels):
+        ctx.sizes = [tuple(t.shape[-2:]) for t in levels]
+        out = ops.lap_collapse(levels)
+        return out.clone() if len(levels) == 1 else out   # a one-level pyramid is its own collapse
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = [g]
+        for size in ctx.sizes[1:]:
+            grads.append(ops.resize_bilinear_adjoint(grads[-1], size))
+        return tuple(grads)
+
+
 def channel_stats(x, unbiased=True, eps=0.0):
     if torch.is_grad_enabled() and x.requires_grad:
         return ChannelStatsFn.apply(x, unbiased, eps)
@@ -718,6 +757,24 @@ class SelfSimLossFn(torch.autograd.Function):
     def backward(ctx, g):
         x, *state = ctx.saved_tensors
         return ops.selfsim_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None
+
+
+class MomentLossFn(torch.autograd.Function):
+    """weight * the moment-matching style loss between x and the target statistics (y_mean, y_cov) of
+    ops.moment_stats (ops.moment_loss); the target is data (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, y_mean, y_cov, weight):
+        x = _dev(x, "t_cs_map")
+        loss, state = ops.moment_loss(x, y_mean, y_cov, float(weight), acc=_acc(x))
+        ctx.save_for_backward(x, *state[:3])
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, *state = ctx.saved_tensors
+        return ops.moment_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None, None
 
 
 class CxLossFn(torch.autograd.Function):

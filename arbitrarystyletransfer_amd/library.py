@@ -24,6 +24,7 @@ hist_loss               losses.py:84-87 (SingleDimHist + EMD)        d x
 remd_loss               -- (relaxed EMD: two-way cosine match)       d x
 selfsim_loss            -- (self-similarity of pixel-pair distances) d x
 cx_loss                 -- (contextual loss: softmax over a cosine match) d x
+moment_loss             -- (STROTSS moment matching: L1 of mean and covariance) d x
 range_loss              train.py:259                                 d x
 sqdiff_mean             train.py:268                                 d x
 mb_expand_dw            mobilenetv2.py:153-161 (to the SE pool)      -- (eval BN folded: inference)
@@ -33,6 +34,7 @@ mb_expand_gemm          models.py:335 (ada_out expand half)          --
 mb_conv3x3_dense        mobilenetv2.py:38-43, models.py:300-316      --
 color_convert           model_util.py:11-140 (six conversions)       d x
 luma_transfer           -- (colour-preserving recombination)         --
+resize_bilinear         F.interpolate(bilinear, align_corners=False) (+ add)   d x (the adjoint kernel), d add
 resize_labels           -- (nearest resize of uint8 label maps)      --
 region_stats            -- (masked per-region channel statistics)    --
 adain_regions           -- (regional multi-style AdaIN)              --
@@ -538,6 +540,35 @@ def _cx_backward(ctx, g, *_):
 register_autograd("ast_hip::cx_loss", _cx_backward, setup_context=_cx_setup)
 
 
+@custom_op("ast_hip::moment_loss", mutates_args=())
+def moment_loss(x: Tensor, y_mean: Tensor, y_cov: Tensor, weight: float) -> Tuple[Tensor, Tensor, Tensor, Tensor,
+                                                                                  Tensor]:
+    """weight * the moment-matching style loss of ops.moment_loss against the statistics of
+    ops.moment_stats; outputs (loss, per_sample, mean_x, sign_mu, sign_cov)."""
+    loss, (mean_x, sign_mu, sign_cov, sums) = ops.moment_loss(x, y_mean, y_cov, float(weight), acc=_acc(x))
+    return loss, sums, mean_x, sign_mu, sign_cov
+
+
+@register_fake("ast_hip::moment_loss")
+def _(x, y_mean, y_cov, weight):
+    n, c = x.shape[:2]
+    return (x.new_empty(()), x.new_empty((n,)), x.new_empty((n, c)), x.new_empty((n, c), dtype=torch.int8),
+            x.new_empty((n, c, c), dtype=torch.int8))
+
+
+def _moment_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], *output[2:])
+    ctx.weight = float(inputs[3])
+
+
+def _moment_backward(ctx, g, *_):
+    x, *state = ctx.saved_tensors
+    return ops.moment_loss_backward(x, tuple(state), g.contiguous(), ctx.weight), None, None, None
+
+
+register_autograd("ast_hip::moment_loss", _moment_backward, setup_context=_moment_setup)
+
+
 @custom_op("ast_hip::range_loss", mutates_args=())
 def range_loss(x: Tensor, weight: float) -> Tensor:
     acc = _acc(x)
@@ -750,6 +781,53 @@ def luma_transfer(stylised: Tensor, content: Tensor) -> Tensor:
 @register_fake("ast_hip::luma_transfer")
 def _(stylised, content):
     return content.new_empty(content.shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# Bilinear resize and its adjoint (csrc/pyramid.hip): the Laplacian pyramid's level step
+# ------------------------------------------------------------------------------------------------
+
+@custom_op("ast_hip::resize_bilinear", mutates_args=())
+def resize_bilinear(x: Tensor, height: int, width: int, add: Optional[Tensor], sign: float) -> Tensor:
+    """F.interpolate(x, (height, width), mode="bilinear", align_corners=False) on fp32 planes; with
+    `add` the result is add + sign * resize(x)."""
+    return ops.resize_bilinear(x, (height, width), add=add, sign=sign)
+
+
+@register_fake("ast_hip::resize_bilinear")
+def _(x, height, width, add, sign):
+    return x.new_empty(tuple(x.shape[:-2]) + (height, width))
+
+
+@custom_op("ast_hip::resize_bilinear_adjoint", mutates_args=())
+def resize_bilinear_adjoint(grad: Tensor, height: int, width: int) -> Tensor:
+    """The transpose of resize_bilinear from (height, width): an op of its own, so that a traced
+    backward sees an opaque kernel with a fake implementation."""
+    return ops.resize_bilinear_adjoint(grad, (height, width))
+
+
+@register_fake("ast_hip::resize_bilinear_adjoint")
+def _(grad, height, width):
+    return grad.new_empty(tuple(grad.shape[:-2]) + (height, width))
+
+
+def _resize_setup(ctx, inputs, output):
+    x, _, _, add, sign = inputs
+    ctx.in_size = (int(x.shape[-2]), int(x.shape[-1]))
+    ctx.sign = float(sign) if add is not None else 1.0
+    ctx.has_add = add is not None
+
+
+def _resize_backward(ctx, g):
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.ops.ast_hip.resize_bilinear_adjoint(g.contiguous(), ctx.in_size[0], ctx.in_size[1])
+        if ctx.sign != 1.0:
+            dx = dx * ctx.sign
+    return dx, None, None, g if ctx.has_add and ctx.needs_input_grad[3] else None, None
+
+
+register_autograd("ast_hip::resize_bilinear", _resize_backward, setup_context=_resize_setup)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -983,8 +1061,8 @@ def _(labels, regions, passes):
 
 
 OPS: List[str] = ["conv3x3", "adain_map", "content_mvn_loss", "style_loss", "huber_loss", "tv_loss", "hist_loss",
-                  "remd_loss", "selfsim_loss", "cx_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw",
+                  "remd_loss", "selfsim_loss", "cx_loss", "moment_loss", "range_loss", "sqdiff_mean", "mb_expand_dw", "mb_se_fold", "mb_pw",
                   "mb_expand_gemm", "mb_conv3x3_dense", "color_convert", "color_convert_backward", "luma_transfer",
-                  "resize_labels",
+                  "resize_bilinear", "resize_bilinear_adjoint", "resize_labels",
                   "region_stats", "adain_regions", "efdm", "plane_sort", "efdm_regions", "wct", "wct_regions",
                   "style_swap", "style_swap_guided", "kmeans", "kmeans_assign", "label_mode_filter"]

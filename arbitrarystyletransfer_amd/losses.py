@@ -8,7 +8,7 @@ from __future__ import annotations
 
 from . import functional as Fn
 from . import library  # noqa: F401  (registers torch.ops.ast_hip.*)
-from .ops import _dev
+from .ops import _dev, moment_stats
 
 import torch
 import torch.nn as nn
@@ -62,7 +62,8 @@ __all__ = ["gram_matrix", "compute_content_loss", "compute_style_loss", "tv_loss
            "content_mvn_loss", "style_loss_weighted", "content_style_loss", "EarthMoversDistanceLoss",
            "HistLayerBase",
            "SingleDimHistLayer", "hist", "earth_movers", "out_of_range_loss", "pixel_mse_loss",
-           "compute_efdm_loss", "compute_remd_loss", "compute_selfsim_loss", "compute_contextual_loss"]
+           "compute_efdm_loss", "compute_remd_loss", "compute_selfsim_loss", "compute_contextual_loss",
+           "compute_moment_loss"]
 
 
 def gram_matrix(tensor):
@@ -196,6 +197,22 @@ def compute_contextual_loss(t_cs_map, target_map, weight: float = 1.0, h: float 
     the HIP backward (torch.ops.ast_hip.cx_loss)."""
     x, y = _dev(t_cs_map, "t_cs_map"), _dev(target_map.detach(), "target_map")
     return _ops.cx_loss(x, y, float(weight), float(h), bool(center))[0]
+
+
+def compute_moment_loss(t_cs_map, style_map, weight: float = 1.0):
+    """The moment-matching style loss of one loss tap (the l_m of Kolkin et al., STROTSS, CVPR 2019): weight *
+    mean over the batch of mean_c |mu_x - mu_y| + mean_ij |Cov_x - Cov_y|, the channel means and unbiased
+    covariances (no ridge) over the pixels of t_cs_map [N, C, H, W] and of style_map [N or 1, C, Hs, Ws]
+    (any size). The style map is detached: its statistics are ops.moment_stats under no_grad; the gradient
+    reaches t_cs_map through the HIP backward (torch.ops.ast_hip.moment_loss). A caller that keeps one
+    style over many steps computes the statistics once and calls the op with them."""
+    x, y = _dev(t_cs_map, "t_cs_map"), _dev(style_map.detach(), "style_map")
+    if x.dim() != 4 or y.dim() != 4 or x.shape[1] != y.shape[1] or y.shape[0] not in (1, x.shape[0]):
+        raise Fn.HipOpError(f"moment loss needs NCHW maps with equal C and a style batch of N or 1: "
+                            f"{tuple(x.shape)} vs {tuple(y.shape)}")
+    with torch.no_grad():
+        y_mean, y_cov = moment_stats(y)
+    return _ops.moment_loss(x, y_mean, y_cov, float(weight))[0]
 
 
 def out_of_range_loss(img, weight: float = 1e8):

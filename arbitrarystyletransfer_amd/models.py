@@ -572,6 +572,13 @@ class AdaINStyleTransfer(nn.Module):
             return _luma_transfer(out, content_img)
         return out
 
+    def refine(self, content_img, style_img, stylizer, **kw):
+        """The feed-forward result polished by optimisation: `stylizer` (strotss.StrotssStylizer) starts
+        from self(content_img, style_img) instead of the content image; **kw as its stylize()."""
+        with torch.no_grad():
+            init = self(content_img, style_img)
+        return stylizer.stylize(content_img, style_img, init=init, **kw)
+
     def stylize_swap(self, content_img, style_img, alpha: float = 1.0, normalize: bool = False,
                      preserve_color: bool = False):
         """Stylise by style swap (StyleSwap on the relu4_1 maps) instead of the model's feature

@@ -1196,6 +1196,100 @@ def cx_loss_backward(x: torch.Tensor, y: torch.Tensor, state, grad: torch.Tensor
     return dx
 
 
+# Moment-matching style loss (csrc/moment.hip): AST_MOMENT_MAX_C of ast_hip.h
+MOMENT_MAX_C = 1024
+
+
+def _moment_map(x: torch.Tensor, name: str, what: str):
+    """An fp32 device NCHW map inside the limits of csrc/moment.hip: (x, n, c, pixels)."""
+    x = _dev(x, name)
+    if x.dim() != 4 or x.numel() == 0:
+        raise HipOpError(f"{what} needs a non-empty NCHW map, got {name} {tuple(x.shape)}")
+    n, c, m = int(x.shape[0]), int(x.shape[1]), int(x.shape[2] * x.shape[3])
+    if c > MOMENT_MAX_C or m < 2 or n > 32767:
+        raise HipOpError(f"{what}: C is at most {MOMENT_MAX_C}, a map has at least 2 pixels and a batch at most "
+                         f"32767 samples: {name} {tuple(x.shape)}")
+    return x, n, c, m
+
+
+def _moment_like(t, dev, shape, dtype, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise HipOpError(f"{what} must be a {dtype} tensor {tuple(shape)} on {dev}")
+    return t.contiguous()
+
+
+def moment_stats(y: torch.Tensor, _splits: int = 0):
+    """(mean [N, C], cov [N, C, C]) of the pixels of y [N, C, H, W]: cov = (Y - mean)(Y - mean)^T / (HW - 1)
+    with no ridge, symmetric in bits. The target side of moment_loss: compute it once per style.
+    _splits (tests) forces the number of pixel splits (0: the library's choice)."""
+    y, n, c, p = _moment_map(y, "y", "moment_stats")
+    L, dev = lib(), y.device
+    nb = int(L.ast_moment_stats_workspace_bytes(n, c, p, int(_splits)))
+    wsb = _ws_bytes(nb, "moment_stats workspace", dev)
+    mean = torch.empty((n, c), device=dev, dtype=torch.float32)
+    cov = torch.empty((n, c, c), device=dev, dtype=torch.float32)
+    pairs = ((c + 63) // 64) * ((c + 63) // 64 + 1) // 2
+    check(_timed(f"moment_stats {c}ch {p}", 2 * n * pairs * 4096 * p, dev, lambda: L.ast_moment_stats_f32(
+        ptr(y), ptr(mean), ptr(cov), n, c, p, int(_splits), ptr(wsb), nb, stream_ptr(dev))), "moment_stats")
+    return mean, cov
+
+
+def moment_loss(x: torch.Tensor, y_mean: torch.Tensor, y_cov: torch.Tensor, weight: float = 1.0, acc=None,
+                _splits: int = 0):
+    """The moment-matching style loss of STROTSS (Kolkin et al., CVPR 2019) between x [N, C, H, W] and the
+    statistics (y_mean [Ns, C], y_cov [Ns, C, C], Ns = N or 1) of moment_stats: weight * mean over the batch
+    of mean_c |mu_x - mu_y| + mean_ij |Cov_x - Cov_y|. Returns (loss, state) with state = (mean_x [N, C],
+    sign_mu int8 [N, C], sign_cov int8 [N, C, C], sums [N], the per-sample terms): what moment_loss_backward
+    reads. Cov_x is never stored. `acc`: the loss accumulator the value is added into (a fresh one if
+    None)."""
+    x, n, c, m = _moment_map(x, "x", "moment_loss")
+    L, dev = lib(), x.device
+    if not isinstance(y_mean, torch.Tensor) or y_mean.dim() != 2 or y_mean.shape[0] not in (1, n):
+        raise HipOpError(f"moment_loss: y_mean must be [N or 1, {c}], got "
+                         f"{tuple(y_mean.shape) if isinstance(y_mean, torch.Tensor) else y_mean!r}")
+    ns = int(y_mean.shape[0])
+    y_mean = _moment_like(y_mean, dev, (ns, c), torch.float32, "moment_loss: y_mean")
+    y_cov = _moment_like(y_cov, dev, (ns, c, c), torch.float32, "moment_loss: y_cov")
+    nb = int(L.ast_moment_loss_workspace_bytes(n, c, m, int(_splits)))
+    wsb = _ws_bytes(nb, "moment_loss workspace", dev)
+    mean_x = torch.empty((n, c), device=dev, dtype=torch.float32)
+    sign_mu = torch.empty((n, c), device=dev, dtype=torch.int8)
+    sign_cov = torch.empty((n, c, c), device=dev, dtype=torch.int8)
+    sums = torch.empty((n,), device=dev, dtype=torch.float32)
+    acc = loss_accumulator(dev) if acc is None else acc
+    pairs = ((c + 63) // 64) * ((c + 63) // 64 + 1) // 2
+    check(_timed(f"moment_loss {c}ch {m}", 2 * n * pairs * 4096 * m, dev, lambda: L.ast_moment_loss_f32(
+        ptr(x), ptr(y_mean), ptr(y_cov), ptr(mean_x), ptr(sign_mu), ptr(sign_cov), ptr(sums), ptr(acc), n, ns, c, m,
+        float(weight), int(_splits), ptr(wsb), nb, stream_ptr(dev))), "moment_loss")
+    return acc[0], (mean_x, sign_mu, sign_cov, sums)
+
+
+def moment_loss_backward(x: torch.Tensor, state, grad: torch.Tensor = None, weight: float = 1.0,
+                         out: torch.Tensor = None) -> torch.Tensor:
+    """d loss / d x [N, C, H, W] of moment_loss from its state, scaled by the device scalar `grad` (None:
+    1); nothing flows to the target. One GEMM launch, sign_cov (X - mean_x) per sample. With `out` the
+    gradient is added into it."""
+    x, n, c, m = _moment_map(x, "x", "moment_loss_backward")
+    if not isinstance(state, (tuple, list)) or len(state) < 3:
+        raise HipOpError("moment_loss_backward needs the state of moment_loss")
+    dev, what = x.device, "moment_loss_backward: {}"
+    mean_x = _moment_like(state[0], dev, (n, c), torch.float32, what.format("mean_x"))
+    sign_mu = _moment_like(state[1], dev, (n, c), torch.int8, what.format("sign_mu"))
+    sign_cov = _moment_like(state[2], dev, (n, c, c), torch.int8, what.format("sign_cov"))
+    if grad is not None:
+        grad = _moment_like(grad.reshape(()) if isinstance(grad, torch.Tensor) and grad.numel() == 1 else grad, dev,
+                            (), torch.float32, what.format("grad"))
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or not out.is_contiguous():
+            raise HipOpError("moment_loss_backward: out must be a contiguous tensor")
+        out = _moment_like(out, dev, x.shape, torch.float32, what.format("out"))
+    dx = out if out is not None else torch.empty_like(x)
+    check(_timed(f"moment_loss_backward {c}ch {m}", 2 * n * c * c * m, dev, lambda: lib().ast_moment_loss_backward_f32(
+        ptr(x), ptr(mean_x), ptr(sign_mu), ptr(sign_cov), ptr(grad), ptr(dx), n, c, m, float(weight),
+        1 if out is not None else 0, stream_ptr(dev))), "moment_loss_backward")
+    return dx
+
+
 # Guided style swap (csrc/swap.hip): a class >= SWAP_MAX_CLASSES takes no part in the match
 SWAP_MAX_CLASSES = 64
 _SWAP_NO_SKIP = 1   # AST_SWAP_NO_SKIP
@@ -1538,6 +1632,112 @@ def luma_transfer(stylised: torch.Tensor, content: torch.Tensor):
     check(_timed(f"luma_transfer {content.shape[2]}x{content.shape[3]}", -nbytes, content.device, lambda: fn(
         ptr(stylised), ptr(content), ptr(out), n, hw, stream_ptr(content.device))), "luma_transfer")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Bilinear resize, its adjoint and the Laplacian pyramid (csrc/pyramid.hip)
+# ------------------------------------------------------------------------------------------------
+
+RESIZE_MAX_SIDE = 4096
+
+
+def _resize_size(size, what: str):
+    try:
+        h, w = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise HipOpError(f"{what} must be (height, width), got {size!r}") from None
+    if not (1 <= h <= RESIZE_MAX_SIDE and 1 <= w <= RESIZE_MAX_SIDE):
+        raise HipOpError(f"{what} must have sides in 1..{RESIZE_MAX_SIDE}, got {(h, w)}")
+    return h, w
+
+
+def _resize_planes(t: torch.Tensor, name: str) -> torch.Tensor:
+    t = _dev(t, name)
+    if t.dim() < 2 or t.numel() == 0:
+        raise HipOpError(f"{name} must be [..., H, W] and not empty, got {tuple(t.shape)}")
+    _resize_size(t.shape[-2:], f"{name}'s size")
+    return t
+
+
+def resize_bilinear(x: torch.Tensor, size, add: torch.Tensor = None, sign: float = 1.0):
+    """F.interpolate(x, size, mode="bilinear", align_corners=False, antialias=False) on the planes
+    of x [..., h, w] (fp32), any ratio; with `add` [..., H, W] the result is add + sign * resize(x)
+    in the same launch (a level of lap_build / lap_collapse)."""
+    x = _resize_planes(x, "x")
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    H, W = _resize_size(size, "size")
+    shape = tuple(x.shape[:-2]) + (H, W)
+    if add is not None:
+        add = _dev(add, "add")
+        if tuple(add.shape) != shape or add.device != x.device:
+            raise HipOpError(f"resize_bilinear: add must be {shape} on {x.device}, got {tuple(add.shape)} on "
+                             f"{add.device}")
+    planes = x.numel() // (h * w)
+    out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    nbytes = 4 * (x.numel() + out.numel() * (2 if add is not None else 1))
+    check(_timed(f"resize {h}x{w}->{H}x{W}", -nbytes, x.device, lambda: lib().ast_resize_bilinear_f32(
+        ptr(x), ptr(out), planes, h, w, H, W, ptr(add), float(sign), stream_ptr(x.device))),
+        "resize_bilinear")
+    return out
+
+
+def resize_bilinear_adjoint(g: torch.Tensor, in_size, out: torch.Tensor = None):
+    """The transpose of resize_bilinear: g [..., H, W] -> [..., h, w] with in_size = (h, w), so that
+    <resize(x), g> = <x, adjoint(g)>. With `out` [..., h, w] the result is added into it."""
+    g = _resize_planes(g, "grad")
+    H, W = int(g.shape[-2]), int(g.shape[-1])
+    h, w = _resize_size(in_size, "in_size")
+    shape = tuple(g.shape[:-2]) + (h, w)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape
+                or out.device != g.device or not out.is_contiguous()):
+            raise HipOpError(f"resize_bilinear_adjoint: out must be a contiguous float32 {shape} on {g.device}")
+        dx = out
+    else:
+        dx = torch.empty(shape, device=g.device, dtype=torch.float32)
+    planes = g.numel() // (H * W)
+    nbytes = 4 * (g.numel() + dx.numel() * (2 if out is not None else 1))
+    check(_timed(f"resize adjoint {H}x{W}->{h}x{w}", -nbytes, g.device, lambda: lib().ast_resize_bilinear_adjoint_f32(
+        ptr(g), ptr(dx), planes, h, w, H, W, 1 if out is not None else 0, stream_ptr(g.device))),
+        "resize_bilinear_adjoint")
+    return dx
+
+
+def lap_down_size(size):
+    """The next coarser pyramid size: (max(h // 2, 1), max(w // 2, 1))."""
+    return max(int(size[0]) // 2, 1), max(int(size[1]) // 2, 1)
+
+
+def lap_build(x: torch.Tensor, levels: int):
+    """The Laplacian pyramid of STROTSS on x [..., H, W]: for l in 0..levels-1,
+    lap_l = cur - resize(down(cur), size(cur)) and cur = down(cur), with down the bilinear resize
+    to lap_down_size. Returns [lap_0, ..., lap_{levels-1}, cur]: two launches per level."""
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 0:
+        raise HipOpError(f"lap_build: levels must be an int >= 0, got {levels!r}")
+    cur = _resize_planes(x, "x")
+    pyr = []
+    for _ in range(levels):
+        small = resize_bilinear(cur, lap_down_size(cur.shape[-2:]))
+        pyr.append(resize_bilinear(small, cur.shape[-2:], add=cur, sign=-1.0))
+        cur = small
+    pyr.append(cur)
+    return pyr
+
+
+def lap_collapse(pyr):
+    """The inverse of lap_build: cur = pyr[-1], then from coarse to fine
+    cur = pyr[l] + resize(cur, size(pyr[l])); one launch per level."""
+    pyr = list(pyr)
+    if not pyr:
+        raise HipOpError("lap_collapse: the pyramid is empty")
+    cur = _resize_planes(pyr[-1], "pyr[-1]")
+    for l in range(len(pyr) - 2, -1, -1):
+        lvl = _resize_planes(pyr[l], f"pyr[{l}]")
+        if lvl.shape[:-2] != cur.shape[:-2]:
+            raise HipOpError(f"lap_collapse: pyr[{l}] is {tuple(lvl.shape)} but the coarser level is "
+                             f"{tuple(cur.shape)}")
+        cur = resize_bilinear(cur, lvl.shape[-2:], add=lvl, sign=1.0)
+    return cur
 
 
 def plane_normalize(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):

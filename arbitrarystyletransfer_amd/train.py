@@ -27,6 +27,10 @@ With `selfsim_lam > 0` (an extension likewise) it adds the self-similarity conte
 between the stylised and the content features at `selfsim_taps` (losses.compute_selfsim_loss):
   loss        += selfsim_lam * sum_taps selfsim(lossnet(stylised)[tap], lossnet(content)[tap])
 a batch-mean term too; at the default selfsim_lam = 0 nothing is launched.
+With `moment_lam > 0` (the third term of that paper) it adds the moment-matching loss between the stylised
+and the style features at `moment_taps` (losses.compute_moment_loss):
+  loss        += moment_lam * sum_taps moment(lossnet(stylised)[tap], lossnet(style)[tap])
+a batch-mean term; at the default moment_lam = 0 nothing is launched.
 With `cx_lam > 0` (an extension likewise) it adds the contextual loss (losses.compute_contextual_loss, bandwidth
 `cx_h`) between the stylised and the style features at `cx_taps`, with `cx_content_lam > 0` the same loss
 against the content features at `cx_content_taps`:
@@ -156,6 +160,11 @@ REMD_TAPS = ("relu_9", "relu_15")
 SELFSIM_TAPS = ("relu_9", "relu_15")
 
 
+# The taps of the moment-matching term (losses.compute_moment_loss): the same two; a tap costs
+# pixels * channels^2.
+MOMENT_TAPS = ("relu_9", "relu_15")
+
+
 # The taps of the contextual terms (losses.compute_contextual_loss): against the style at both maps, against
 # the content at relu5_1; a tap's map may have at most ops.CX_MAX_PIXELS pixels.
 CX_TAPS = ("relu_9", "relu_15")
@@ -172,7 +181,7 @@ def default_args(**kw):
     a = dict(train_iter=10, batch_size=8, lr=2e-4, content_lam=1.25, style_lam=0.5, tv_lam=0.0006, lf_lam=1.0,
              org_img_lam=0.5, save_dir="models/ast/", load=False, image_size=512, full_losses=False,
              remd_lam=0.0, remd_taps=REMD_TAPS, selfsim_lam=0.0, selfsim_taps=SELFSIM_TAPS,
-             cx_lam=0.0, cx_taps=CX_TAPS, cx_content_lam=0.0, cx_content_taps=CX_CONTENT_TAPS, cx_h=0.5)
+             moment_lam=0.0, moment_taps=MOMENT_TAPS, cx_lam=0.0, cx_taps=CX_TAPS, cx_content_lam=0.0, cx_content_taps=CX_CONTENT_TAPS, cx_h=0.5)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -253,6 +262,13 @@ class AdaINTrainer:
             mean_terms = mean_terms + selfsim_lam * selfsim_loss
             loss = loss + selfsim_lam * selfsim_loss
             out.update(loss=loss, selfsim_loss=selfsim_loss)
+        moment_lam = float(getattr(a, "moment_lam", 0.0))
+        if moment_lam > 0:   # the moment-matching style term; nothing is launched without it
+            mom_idx = [_tap_index(k, "moment_taps") for k in getattr(a, "moment_taps", MOMENT_TAPS)]
+            moment_loss = torch.stack([L.compute_moment_loss(s_taps[i], taps[i][b:]) for i in mom_idx]).sum()
+            mean_terms = mean_terms + moment_lam * moment_loss
+            loss = loss + moment_lam * moment_loss
+            out.update(loss=loss, moment_loss=moment_loss)
         cx_lam, cx_content_lam = float(getattr(a, "cx_lam", 0.0)), float(getattr(a, "cx_content_lam", 0.0))
         cx_h = float(getattr(a, "cx_h", 0.5))
         if cx_lam > 0:   # the contextual style term; nothing is launched without it

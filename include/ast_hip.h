@@ -1337,6 +1337,85 @@ int ast_luma_transfer_f32(const float* stylised, const float* content, float* ou
 int ast_luma_transfer_bf16(const void* stylised, const void* content, void* out, int n, long long hw,
                            void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Moment-matching style loss (the l_m of Kolkin et al., STROTSS, CVPR 2019, its `moment_loss`;
+ * csrc/moment.hip; an extension, no reference counterpart): L1 distance between the channel means and
+ * between the channel covariances of two maps, with a backward to the first. tests/moment_ref.py
+ * restates the definition.
+ * Inputs, fp32 dense NCHW with the spatial sides flattened: x [n, c, m], the differentiable side, and
+ * the target y [ns, c, p], ns == n or ns == 1 (one style shared by the batch), of any size p; the loss
+ * sees y only through its statistics. Limits: c in 1..AST_MOMENT_MAX_C, m and p in 2..2^31 - 1,
+ * n <= 32767.
+ * Statistics, per sample: mu = the mean over the pixels, computed as x_0 + sum(x - x_0) / m (exact for a
+ * constant plane); Cov = (X - mu)(X - mu)^T / (m - 1), with no ridge, the products summed on the fp32
+ * matrix cores over the upper-triangle 64x64 tiles, split along the pixels, the splits added in split
+ * order; Cov is symmetric in bits. `splits`: 0 = the library's choice, else that many (clamped so that
+ * every split has pixels; a test hook: the result depends on it only by rounding).
+ * Loss: L_b = (1 / c) sum_i |mu_x - mu_y|_i + (1 / c^2) sum_ij |Cov_x - Cov_y|_ij; sums[b] = L_b;
+ * *loss += weight / n * sum_b L_b, the samples in a fixed order. loss is a loss accumulator
+ * (AST_LOSS_ACC_FLOATS floats, above). Cov_x is never stored.
+ * Signs: sign_mu [n, c] = sign(mu_x - mu_y) and sign_cov [n, c, c] = sign(Cov_x - Cov_y), int8 with
+ * values +1, -1 and 0 for a difference that is zero or NaN; sign_cov is computed on the upper-triangle
+ * tiles and mirrored, so it is symmetric in bits.
+ * Backward, to x only (the target is data). With g = *gscale (a device scalar; NULL: 1):
+ *   dx[b, i, k] (+)= g weight / n (sign_mu[i] / (c m)
+ *                                  + 2 / (c^2 (m - 1)) sum_j sign_cov[i, j] (x[j, k] - mu_x[j]))
+ * one GEMM per sample, j ascending in pairs (the MFMA's order); the centring projection of the
+ * covariance drops out because the rows of X - mu sum to zero. accumulate != 0 adds into dx, else every
+ * element of dx is written.
+ * Non-finite values: a NaN or infinity in sample b of x makes mu_x, Cov entries, sums[b] and hence
+ * *loss non-finite; a NaN difference has sign 0, an infinite one its sign; dx of sample b is what the
+ * GEMM gives on those values. Every other sample's sums, signs and dx are unchanged in bits: a sample
+ * is a grid index in every launch.
+ * No floating-point atomics, no host synchronisation, no allocation. Workspaces are device memory,
+ * 256-byte aligned, of at least the matching *_workspace_bytes query: the partial tiles,
+ * 4 n splits pairs 64^2 bytes with pairs = t (t + 1) / 2, t = ceil(c / 64), and for the loss one
+ * partial sum per sample and tile pair, each rounded up to 256.
+ * AST_E_NULLPTR: a null pointer (gscale may be null). AST_E_SHAPE: a size out of the limits above, ns
+ * outside {1, n}, a short workspace. AST_E_UNSUPPORTED: c > AST_MOMENT_MAX_C, splits < 0. The queries
+ * return the same negative codes. All checks run before the first launch. */
+#define AST_MOMENT_MAX_C 1024
+
+/* mean [n, c] and cov [n, c, c] of y [n, c, m]; three launches. */
+long long ast_moment_stats_workspace_bytes(int n, int c, long long m, int splits);
+int ast_moment_stats_f32(const float* y, float* mean, float* cov, int n, int c, long long m, int splits,
+                         void* workspace, long long workspace_bytes, void* stream);
+
+/* The forward from x and the target's statistics y_mean [ns, c], y_cov [ns, c, c]; five launches.
+ * mean_x [n, c], sign_mu and sign_cov are what the backward reads. */
+long long ast_moment_loss_workspace_bytes(int n, int c, long long m, int splits);
+int ast_moment_loss_f32(const float* x, const float* y_mean, const float* y_cov, float* mean_x,
+                        signed char* sign_mu, signed char* sign_cov, float* sums, float* loss, int n, int ns,
+                        int c, long long m, float weight, int splits, void* workspace,
+                        long long workspace_bytes, void* stream);
+
+/* dx [n, c, m] from the forward's state; one launch, 2 c^2 m FLOP per sample, no workspace. */
+int ast_moment_loss_backward_f32(const float* x, const float* mean_x, const signed char* sign_mu,
+                                 const signed char* sign_cov, const float* gscale, float* dx, int n, int c,
+                                 long long m, float weight, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Bilinear resize of fp32 planes and its adjoint (csrc/pyramid.hip): x [planes][h][w] ->
+ * out [planes][H][W], every side in 1..4096, any ratio. The filter is
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=False):
+ *   scale = (float)in / out;  s = max(scale * (o + 0.5) - 0.5, 0);  i0 = min((int)s, in - 1);
+ *   i1 = min(i0 + 1, in - 1);  l1 = s - i0;  value = (1 - l1) * x[i0] + l1 * x[i1]   per axis
+ * (not the antialiased filter of ast_aug_resize_f32). With `add` [planes][H][W] non-null,
+ * out = add + add_sign * resize(x); out must not alias add or x. This one launch is a level of the
+ * Laplacian pyramid both ways: lap = cur - resize(down(cur)) (add_sign -1) and
+ * cur = lap + resize(cur) (add_sign +1).
+ * The adjoint is the transpose: dx [planes][h][w] = R^T g for g [planes][H][W] (accumulate != 0:
+ * dx += R^T g). One thread owns a source pixel and sums, in ascending (oy, ox) order, the outputs
+ * that have a non-zero weight on it, so two runs agree in bits; a non-finite g reaches only those
+ * source pixels (PyTorch's autograd also adds 0 * g to a cell's second pixel when l1 = 0). A source pixel feeding k outputs costs k serial steps (fine for the pyramid's
+ * factor 2; 1 -> 4096 per side is 16M steps in one thread).
+ * No workspace, no atomics, no host synchronisation. AST_E_SHAPE for planes <= 0 or a side outside
+ * 1..4096. */
+int ast_resize_bilinear_f32(const float* x, float* out, int planes, int h, int w, int H, int W,
+                            const float* add, float add_sign, void* stream);
+int ast_resize_bilinear_adjoint_f32(const float* g, float* dx, int planes, int h, int w, int H, int W,
+                                    int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
