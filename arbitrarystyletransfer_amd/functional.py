@@ -1,13 +1,20 @@
 """Autograd for the HIP ops: torch.autograd.Function wrappers whose forward and backward are
 both HIP kernels of libast_hip.so, so `loss.backward()` in a train.py-style loop runs the
 backward on the GPU through the same C ABI (no PyTorch compute on the path).
+
+An op's backward is written once. The eager hot path (the convs, AdaIN, the loss network) uses the
+Function classes here, whose backward bodies are plain functions (conv_act_backward,
+encoder_conv_backward, decoder_conv_backward, adain_backward) that the registered formulas of
+library.py call too. The losses have no Function class: losses.py goes through torch.ops.ast_hip.*,
+and this module keeps only the launch helpers those ops share (gram, mvn_huber, _style_terms,
+soft_histogram).
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from ._lib import HipOpError, check, lib, loss_accumulator, ptr, stream_ptr, workspace
+from ._lib import HipOpError, check, lib, ptr, stream_ptr, workspace
 
 _dev = ops._dev
 
@@ -154,6 +161,68 @@ def conv_weight_grad(x, dy, cout, upsample=1, pad_mode="zeros", with_bias=True, 
     return dw, db
 
 
+def conv_act_backward(pre, g_pre, g_act, g_pool):
+    """dL/d(conv output) of conv -> {pre, ReLU, ReLU + MaxPool2x2} from the gradients of the three taps
+    (an empty or None one is absent). `pre` is the pre-activation or anything of its sign pattern
+    (the ReLU output); the max-pool routing reads its values."""
+    gp, ga, gq = (_dev(g, "g") if (g is not None and g.numel()) else None for g in (g_pre, g_act, g_pool))
+    n, c, h, w = pre.shape
+    dy = torch.empty_like(pre)
+    check(lib().ast_conv_act_backward_f32(ptr(pre), ptr(gp), ptr(ga), ptr(gq), ptr(dy), n * c, h, w, _s(pre)),
+          "conv_act_backward")
+    return dy
+
+
+def encoder_conv_backward(x, weight, pre, mean, std, g_pre, g_act, g_pool, need_x, need_w, has_bias,
+                          params=(None, None)):
+    """(dx, dW, db) of an encoder layer, conv3x3 (zero pad) -> {pre, ReLU, ReLU + MaxPool}: the backward
+    of EncoderConvFn and of ast_hip::conv3x3 with zero padding. std (conv_1) is the input scale of the
+    input gradient; with mean given the weight gradient sees the normalised image. `params` =
+    (weight, bias) parameters for the GRAD_ARENA lookup; without them dW and db are fresh buffers."""
+    dy = conv_act_backward(pre, g_pre, g_act, g_pool)
+    dx = dw = db = None
+    if need_x:
+        dx = conv_input_grad_same(dy, weight, std.view(-1) if std is not None else None)
+    if need_w:
+        xin = normalize_image(x, mean, std) if mean is not None else x
+        dw, db = conv_weight_grad(xin, dy, int(weight.shape[0]), with_bias=has_bias, weight=params[0],
+                                  bias=params[1])
+    return dx, dw, db
+
+
+def decoder_conv_backward(x, weight, g, relu_out, upsample, need_x, need_w, has_bias, mask_input=False,
+                          params=(None, None)):
+    """(dx, dW, db) of a decoder layer, [Upsample x2] -> ReflectionPad(1) -> conv3x3 -> [ReLU]: the
+    backward of DecoderConvFn and of ast_hip::conv3x3 with reflect padding. relu_out: the layer's ReLU
+    output, which masks g here (None: no ReLU, or g arrives masked); mask_input: x is a ReLU output
+    whose backward runs in the input-gradient epilogue; params as in encoder_conv_backward."""
+    dy = g = _dev(g, "grad")
+    if relu_out is not None:
+        dy = torch.empty_like(g)
+        check(lib().ast_relu_mask_f32(ptr(g), ptr(relu_out), ptr(dy), g.numel(), _s(g)), "relu_mask")
+    dx = dw = db = None
+    if need_x:
+        dx = conv_input_grad(dy, weight, upsample, "reflect", mask=x if mask_input else None)
+    if need_w:
+        dw, db = conv_weight_grad(x, dy, int(weight.shape[0]), upsample, "reflect", has_bias, *params)
+    return dx, dw, db
+
+
+def adain_backward(content, style, g, alpha, swap, need_content, need_style):
+    """(d content, d style) of ops.adain, one launch for both: the backward of AdaINFn and of
+    ast_hip::adain_map."""
+    if not (need_content or need_style):
+        return None, None
+    content, style, g = _dev(content, "content"), _dev(style, "style"), _dev(g, "grad")
+    n, c, hc, wc = content.shape
+    hs, ws = style.shape[2:]
+    dc = torch.empty_like(content) if need_content else None
+    ds = torch.empty_like(style) if need_style else None
+    check(lib().ast_adain_backward_f32(ptr(content), ptr(style), ptr(g), ptr(dc), ptr(ds), n, c, hc, wc, hs, ws,
+                                       float(alpha), 1 if swap else 0, _s(g)), "adain_backward")
+    return dc, ds
+
+
 # ------------------------------------------------------------------------------------------------
 # VGG encoder block: conv3x3 (zero pad) -> {pre, ReLU, ReLU+MaxPool} (PretrainedEncoder)
 # ------------------------------------------------------------------------------------------------
@@ -176,25 +245,9 @@ class EncoderConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_pre, g_act, g_pool):
         x, weight, pre, mean, std = ctx.saved_tensors
-        n, cout, h, w = pre.shape
-        gp = g_pre if (g_pre is not None and g_pre.numel()) else None
-        ga = g_act if (g_act is not None and g_act.numel()) else None
-        gq = g_pool if (g_pool is not None and g_pool.numel()) else None
-        dy = torch.empty_like(pre)
-        check(lib().ast_conv_act_backward_f32(ptr(pre), ptr(_dev(gp, "g") if gp is not None else None),
-                                              ptr(_dev(ga, "g") if ga is not None else None),
-                                              ptr(_dev(gq, "g") if gq is not None else None), ptr(dy),
-                                              n * cout, h, w, _s(pre)), "conv_act_backward")
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = conv_input_grad_same(dy, weight, std.view(-1) if std is not None else None)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            xin = x
-            if mean is not None:  # conv_1 sees the normalised image
-                xin = normalize_image(x, mean, std)
-            dw, db = conv_weight_grad(xin, dy, cout, with_bias=ctx.has_bias, weight=ctx.param_ids[0],
-                                      bias=ctx.param_ids[1])
-        return dx, dw, db, None, None, None, None, None
+        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        return encoder_conv_backward(x, weight, pre, mean, std, g_pre, g_act, g_pool, ctx.needs_input_grad[0],
+                                     need_w, ctx.has_bias, ctx.param_ids) + (None,) * 5
 
 
 class LossNetFn(torch.autograd.Function):
@@ -255,14 +308,7 @@ class LossNetFn(torch.autograd.Function):
                 return None
             # act > 0 exactly where pre > 0: a layer without a stored pre-ReLU map (no pool below it)
             # masks by its ReLU output, the next conv's input
-            pre = pres[j] if pres[j] is not None else ins[j + 1]
-            n, c, h, w = pre.shape
-            dy = torch.empty_like(pre)
-            check(lib().ast_conv_act_backward_f32(ptr(pre), ptr(_dev(gp, "g") if gp is not None else None),
-                                                  ptr(_dev(ga, "g") if ga is not None else None),
-                                                  ptr(_dev(gq, "g") if gq is not None else None), ptr(dy),
-                                                  n * c, h, w, _s(pre)), "conv_act_backward")
-            return dy
+            return conv_act_backward(pres[j] if pres[j] is not None else ins[j + 1], gp, ga, gq)
 
         dy = act_backward(L - 1, None)
         for j in range(L - 1, 0, -1):
@@ -319,19 +365,10 @@ class DecoderConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, out = ctx.saved_tensors
-        g = _dev(g, "grad")
-        n, cout, H, W = out.shape
-        if ctx.relu and not ctx.out_premasked:
-            dy = torch.empty_like(g)
-            check(lib().ast_relu_mask_f32(ptr(g), ptr(out), ptr(dy), g.numel(), _s(g)), "relu_mask")
-        else:
-            dy = g
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = conv_input_grad(dy, weight, ctx.upsample, "reflect", mask=x if ctx.mask_input else None)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dw, db = conv_weight_grad(x, dy, cout, ctx.upsample, "reflect", ctx.has_bias, *ctx.param_ids)
-        return (dx, dw, db) + (None,) * (len(ctx.needs_input_grad) - 3)  # 6 or 8 inputs
+        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        grads = decoder_conv_backward(x, weight, g, out if ctx.relu and not ctx.out_premasked else None, ctx.upsample,
+                                      ctx.needs_input_grad[0], need_w, ctx.has_bias, ctx.mask_input, ctx.param_ids)
+        return grads + (None,) * (len(ctx.needs_input_grad) - 3)  # 6 or 8 inputs
 
 
 # ------------------------------------------------------------------------------------------------
@@ -390,17 +427,7 @@ class AdaINFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         content, style = ctx.saved_tensors
-        content, style = _dev(content, "content"), _dev(style, "style")
-        g = _dev(g, "grad")
-        n, c, hc, wc = content.shape
-        hs, ws = style.shape[2:]
-        dc = torch.empty_like(content) if ctx.needs_input_grad[0] else None
-        ds = torch.empty_like(style) if ctx.needs_input_grad[1] else None
-        if dc is None and ds is None:
-            return None, None, None, None
-        check(lib().ast_adain_backward_f32(ptr(content), ptr(style), ptr(g), ptr(dc), ptr(ds), n, c, hc, wc, hs, ws,
-                                           float(ctx.alpha), 1 if ctx.swap else 0, _s(g)), "adain_backward")
-        return dc, ds, None, None
+        return adain_backward(content, style, g, ctx.alpha, ctx.swap, *ctx.needs_input_grad[:2]) + (None, None)
 
 
 class EFDMFn(torch.autograd.Function):
@@ -439,27 +466,6 @@ def color_convert(x, mode):
     return ops.color_convert(x, mode)
 
 
-class ResizeBilinearFn(torch.autograd.Function):
-    """ops.resize_bilinear(x, size, add, sign) with the HIP adjoint as its backward:
-    d x = sign * R^T g (one launch), d add = g."""
-
-    @staticmethod
-    def forward(ctx, x, size, add=None, sign=1.0):
-        ctx.in_size = tuple(x.shape[-2:])
-        ctx.sign = float(sign) if add is not None else 1.0
-        ctx.has_add = add is not None
-        return ops.resize_bilinear(x, size, add=add, sign=sign)
-
-    @staticmethod
-    def backward(ctx, g):
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.resize_bilinear_adjoint(g, ctx.in_size)
-            if ctx.sign != 1.0:
-                dx = dx.mul_(ctx.sign)
-        return dx, None, g if ctx.has_add and ctx.needs_input_grad[2] else None, None
-
-
 class LapCollapseFn(torch.autograd.Function):
     """ops.lap_collapse(levels) with autograd into every level: level 0 receives g, level l + 1 the
     adjoint of level l's gradient through the resize between them, one adjoint launch per level."""
@@ -491,19 +497,8 @@ def mean_variance_norm(x):
 
 
 # ------------------------------------------------------------------------------------------------
-# Losses (scalar outputs; the backward kernels take grad_output as a device scalar)
+# Launch helpers of the loss ops of library.py (`loss`: the caller's accumulator, _lib.loss_accumulator)
 # ------------------------------------------------------------------------------------------------
-
-def _acc(like):
-    """A loss accumulator (ast_hip.h: value at [0], then the per-workgroup partials that the
-    kernels sum in a fixed order)."""
-    return loss_accumulator(like.device)
-
-
-def _value(acc):
-    """The 0-d loss value of an accumulator (a view of element 0)."""
-    return acc[0]
-
 
 def gram(f, g, scale):
     """g[b] = scale * f[b] f[b]^T for f [b, c, hw] (the deterministic split-K launch)."""
@@ -514,52 +509,6 @@ def gram(f, g, scale):
                      lambda: lib().ast_gram_f32(ptr(f), ptr(g), b, c, hw, scale, ptr(ws), ws.numel(), _s(f))), "gram")
 
 
-class GramFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, f):
-        f = _dev(f, "tensor")
-        b, c, h, w = f.shape
-        g = _empty((b, c, c), f)
-        gram(f, g, 1.0 / (c * h * w))
-        ctx.save_for_backward(f)
-        return g
-
-    @staticmethod
-    def backward(ctx, dg):
-        (f,) = ctx.saved_tensors
-        b, c, h, w = f.shape
-        dg = _dev(dg, "grad")
-        df = torch.empty_like(f)
-        check(lib().ast_gram_backward_f32(ptr(f), ptr(dg), ptr(df), None, None, b, c, h * w, 1.0 / (c * h * w),
-                                          None, 0, _s(f)), "gram_backward")
-        return df
-
-
-class HuberFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y):
-        x, y = _dev(x, "input"), _dev(y, "target")
-        if x.shape != y.shape:
-            raise HipOpError(f"huber: shape mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
-        loss = _acc(x)
-        check(lib().ast_huber_f32(ptr(x), ptr(y), x.numel(), 1.0, None, ptr(loss), None, 0, _s(x)), "huber")
-        ctx.save_for_backward(x, y)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y = ctx.saved_tensors
-        g = _dev(g, "grad")
-        dx = dy = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            check(lib().ast_huber_f32(ptr(x), ptr(y), x.numel(), 1.0, ptr(g), None, ptr(dx), 0, _s(x)), "huber")
-        if ctx.needs_input_grad[1]:
-            dy = torch.empty_like(y)
-            check(lib().ast_huber_f32(ptr(y), ptr(x), y.numel(), 1.0, ptr(g), None, ptr(dy), 0, _s(y)), "huber")
-        return dx, dy
-
-
 def mvn_huber(x, y, weight, loss, pstats):
     """loss += weight * compute_content_loss(mvn(x), mvn(y)); pstats (or None) for the backward.
     The split-plane launch (chunk partials merged in order through a workspace)."""
@@ -568,63 +517,6 @@ def mvn_huber(x, y, weight, loss, pstats):
     ws = workspace(lib().ast_plane_stats_workspace_floats(n * c, hw), x.device)
     check(lib().ast_mvn_huber_ws_f32(ptr(x), ptr(y), n * c, hw, weight, ptr(loss), ptr(pstats), ptr(ws), ws.numel(),
                                      _s(x)), "mvn_huber")
-
-
-class MVNHuberFn(torch.autograd.Function):
-    """compute_content_loss(mean_variance_norm(x), mean_variance_norm(y)) with y detached (as
-    every call site in train.py), one fused kernel for value and gradient."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight):
-        x, y = _dev(x, "x"), _dev(y, "y")
-        if x.shape != y.shape:
-            raise HipOpError(f"content loss: shape mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
-        n, c = x.shape[:2]
-        loss = _acc(x)
-        pstats = _empty((n * c, 6), x) if ctx.needs_input_grad[0] else None
-        mvn_huber(x, y, weight, loss, pstats)
-        ctx.save_for_backward(x, y, pstats)
-        ctx.weight = weight
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y, pstats = ctx.saved_tensors
-        g = _dev(g, "grad")
-        n, c = x.shape[:2]
-        dx = torch.empty_like(x)
-        check(lib().ast_mvn_huber_backward_f32(ptr(x), ptr(y), ptr(pstats), n * c, x[0, 0].numel(), ctx.weight,
-                                               ptr(g), ptr(dx), 0, _s(x)), "mvn_huber_backward")
-        return dx, None, None
-
-
-class StyleLossFn(torch.autograd.Function):
-    """compute_style_loss(x, y) (losses.py:128-139) with y detached: value in forward; the
-    backward recomputes the statistics and Gram matrices and emits dx in two launches
-    (moment terms fused into the Gram-backward GEMM epilogue)."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight):
-        x, y = _dev(x, "x"), _dev(y, "y")
-        if x.shape[:2] != y.shape[:2]:
-            raise HipOpError("style loss: (N, C) mismatch")
-        loss = _acc(x)
-        # with a gradient to come, the forward also keeps dG and the moment-term coefficients
-        # (all linear in grad_output), so the backward is one GEMM with grad_output as a scale
-        dg, ra, rb = _style_terms(x, y, weight, loss, want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(x, dg, ra, rb)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, dg, ra, rb = ctx.saved_tensors
-        b, c, h, w = x.shape
-        dx = torch.empty_like(x)
-        gg = _dev(g, "grad")
-        check(ops._timed(f"gram_bwd {c}x{h * w}", 2 * b * c * c * h * w, x.device,
-                         lambda: lib().ast_gram_backward_f32(ptr(x), ptr(dg), ptr(dx), ptr(ra), ptr(rb), b, c, h * w,
-                                                             1.0 / (c * h * w), ptr(gg), 0, _s(x))), "gram_backward")
-        return dx, None, None
 
 
 def _style_terms(x, y, weight, loss, want_grad):
@@ -653,28 +545,8 @@ def _style_terms(x, y, weight, loss, want_grad):
     return dg, ra, rb
 
 
-class TVLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, img):
-        img = _dev(img, "img")
-        n, c, h, w = img.shape
-        loss = _acc(img)
-        check(lib().ast_tv_loss_f32(ptr(img), n * c, h, w, 1.0, None, ptr(loss), None, 0, _s(img)), "tv_loss")
-        ctx.save_for_backward(img)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        (img,) = ctx.saved_tensors
-        n, c, h, w = img.shape
-        dx = torch.empty_like(img)
-        check(lib().ast_tv_loss_f32(ptr(img), n * c, h, w, 1.0, ptr(_dev(g, "grad")), None, ptr(dx), 0, _s(img)),
-              "tv_loss")
-        return dx
-
-
 # ------------------------------------------------------------------------------------------------
-# Histogram / range / pixel losses (train.py:255-269; SURVEY.md §8f "next" #2)
+# Soft histogram of the histogram loss (train.py:255-269; SURVEY.md §8f "next" #2)
 # ------------------------------------------------------------------------------------------------
 
 HIST_BINS = 256   # HistLayerBase.K, losses.py:44
@@ -690,153 +562,3 @@ def soft_histogram(x):
     check(lib().ast_soft_hist_f32(ptr(x), b, x.numel() // b, 1.0 / (x.shape[1] * x.shape[2]), ptr(hist), ptr(ws),
                                   ws.numel(), _s(x)), "soft_hist")
     return hist
-
-
-class HistLossFn(torch.autograd.Function):
-    """weight * compute_hist_loss(x, y) (losses.py:84-87): EMD between the soft histograms of x
-    and y, mean over the batch; y is data (no gradient), as at train.py:261."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight):
-        x, y = _dev(x, "t_cs"), _dev(y, "style_map")
-        if x.shape[0] != y.shape[0]:
-            raise HipOpError(f"hist loss: batch mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
-        hx, hy = soft_histogram(x), soft_histogram(y)
-        loss = _acc(x)
-        check(lib().ast_emd_loss_f32(ptr(hx), ptr(hy), x.shape[0], float(weight), None, ptr(loss), None, _s(x)),
-              "emd_loss")
-        ctx.save_for_backward(x, hx, hy)
-        ctx.weight = float(weight)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, hx, hy = ctx.saved_tensors
-        g = _dev(g, "grad")
-        b = x.shape[0]
-        ghist = torch.empty_like(hx)
-        check(lib().ast_emd_loss_f32(ptr(hx), ptr(hy), b, ctx.weight, ptr(g), None, ptr(ghist), _s(x)), "emd_loss")
-        dx = torch.empty_like(x)
-        check(lib().ast_soft_hist_backward_f32(ptr(x), b, x.numel() // b, 1.0 / (x.shape[1] * x.shape[2]),
-                                               ptr(ghist), ptr(dx), 0, _s(x)), "soft_hist_backward")
-        return dx, None, None
-
-
-class RemdLossFn(torch.autograd.Function):
-    """weight * the relaxed earth mover's distance between the pixels of x and of y (ops.remd_loss); y
-    is data (no gradient). _branch as in ops.remd_loss."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight, _branch=0):
-        x, y = _dev(x, "t_cs_map"), _dev(y, "style_map")
-        loss, _, _, branch, state = ops.remd_loss(x, y, float(weight), int(_branch), acc=_acc(x))
-        ctx.save_for_backward(x, y, branch, *state)
-        ctx.weight = float(weight)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y, branch, *state = ctx.saved_tensors
-        dx = ops.remd_loss_backward(x, y, tuple(state), branch, _dev(g, "grad"), ctx.weight)
-        return dx, None, None, None
-
-
-class SelfSimLossFn(torch.autograd.Function):
-    """weight * the self-similarity content loss between the pixel-pair distances inside x and inside c
-    (ops.selfsim_loss); c is data (no gradient) and is not saved."""
-
-    @staticmethod
-    def forward(ctx, x, c, weight):
-        x, c = _dev(x, "t_cs_map"), _dev(c, "content_map")
-        loss, _, state = ops.selfsim_loss(x, c, float(weight), acc=_acc(x))
-        ctx.save_for_backward(x, *state)
-        ctx.weight = float(weight)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        x, *state = ctx.saved_tensors
-        return ops.selfsim_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None
-
-
-class MomentLossFn(torch.autograd.Function):
-    """weight * the moment-matching style loss between x and the target statistics (y_mean, y_cov) of
-    ops.moment_stats (ops.moment_loss); the target is data (no gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, y_mean, y_cov, weight):
-        x = _dev(x, "t_cs_map")
-        loss, state = ops.moment_loss(x, y_mean, y_cov, float(weight), acc=_acc(x))
-        ctx.save_for_backward(x, *state[:3])
-        ctx.weight = float(weight)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        x, *state = ctx.saved_tensors
-        return ops.moment_loss_backward(x, tuple(state), _dev(g, "grad"), ctx.weight), None, None, None
-
-
-class CxLossFn(torch.autograd.Function):
-    """weight * the contextual loss between the pixels of x and of y (ops.cx_loss), bandwidth h, centred on
-    y's channel means unless center is off; y is data (no gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight, h=0.5, center=True):
-        x, y = _dev(x, "t_cs_map"), _dev(y, "target_map")
-        loss, _, state = ops.cx_loss(x, y, float(weight), float(h), bool(center), acc=_acc(x))
-        ctx.save_for_backward(x, y, *state)
-        ctx.weight, ctx.h = float(weight), float(h)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y, *state = ctx.saved_tensors
-        dx = ops.cx_loss_backward(x, y, tuple(state), _dev(g, "grad"), ctx.weight, ctx.h)
-        return dx, None, None, None, None
-
-
-class RangeLossFn(torch.autograd.Function):
-    """weight * compute_content_loss(x, torch.clip(x.detach(), 0, 1)) (train.py:259)."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        x = _dev(x, "x")
-        loss = _acc(x)
-        check(lib().ast_range_loss_f32(ptr(x), x.numel(), float(weight), None, ptr(loss), None, 0, _s(x)),
-              "range_loss")
-        ctx.save_for_backward(x)
-        ctx.weight = float(weight)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        (x,) = ctx.saved_tensors
-        dx = torch.empty_like(x)
-        check(lib().ast_range_loss_f32(ptr(x), x.numel(), ctx.weight, ptr(_dev(g, "grad")), None, ptr(dx), 0, _s(x)),
-              "range_loss")
-        return dx, None
-
-
-class SqDiffMeanFn(torch.autograd.Function):
-    """weight * ((y - x) ** 2).mean() with y constant (train.py:268: content_imgs.detach())."""
-
-    @staticmethod
-    def forward(ctx, x, y, weight):
-        x, y = _dev(x, "x"), _dev(y, "y")
-        if x.shape != y.shape:
-            raise HipOpError(f"sqdiff: shape mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
-        loss = _acc(x)
-        check(lib().ast_sqdiff_mean_f32(ptr(x), ptr(y), x.numel(), float(weight), None, ptr(loss), None, 0, _s(x)),
-              "sqdiff")
-        ctx.save_for_backward(x, y)
-        ctx.weight = float(weight)
-        return _value(loss)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y = ctx.saved_tensors
-        dx = torch.empty_like(x)
-        check(lib().ast_sqdiff_mean_f32(ptr(x), ptr(y), x.numel(), ctx.weight, ptr(_dev(g, "grad")), None, ptr(dx), 0,
-                                        _s(x)), "sqdiff")
-        return dx, None, None

@@ -8,7 +8,10 @@ a fake (meta) implementation, so torch.compile / FakeTensor tracing sees shapes 
 kernels -- `torch.compile(models.AdaINStyleTransfer(), fullgraph=True)` traces the forward with no
 graph break -- and the differentiable ones carry their backward formula
 (torch.library.register_autograd), whose kernels are the HIP backward kernels (conv dgrad / wgrad,
-AdaIN backward, the fused loss gradients). The native C++ registration (csrc/torch_ops.cpp,
+AdaIN backward, the fused loss gradients). A backward is written once: conv3x3 and adain_map call the
+bodies they share with the eager Function classes (functional.encoder_conv_backward,
+decoder_conv_backward, adain_backward); the loss formulas below are the only copy, there being no
+Function class for a loss. The native C++ registration (csrc/torch_ops.cpp,
 libast_torch_ops.so: adain, channel_stats, conv3x3_pack, conv3x3_fwd, gram) shares the namespace;
 gram gets its autograd formula here.
 
@@ -115,35 +118,13 @@ def _conv_setup(ctx, inputs, output):
 def _conv_backward(ctx, g_pre, g_act, g_pool):
     x, weight, mask, mean, std = ctx.saved_tensors
     upsample, pad_mode, has_bias, want_act = ctx.cfg
-    cout = int(weight.shape[0])
-    n, cin, hin, win = x.shape
-    H, W = hin * upsample, win * upsample
-    nz = lambda t: t if (t is not None and t.numel()) else None  # noqa: E731
-    dx = dw = db = None
-    if pad_mode == 0:   # the encoder walk (EncoderConvFn): act backward, dgrad, wgrad
-        gp, ga, gq = nz(g_pre), nz(g_act), nz(g_pool)
-        dy = torch.empty_like(mask)
-        check(lib().ast_conv_act_backward_f32(ptr(mask), ptr(gp.contiguous() if gp is not None else None),
-                                              ptr(ga.contiguous() if ga is not None else None),
-                                              ptr(gq.contiguous() if gq is not None else None), ptr(dy),
-                                              n * cout, H, W, stream_ptr(x.device)), "conv_act_backward")
-        if ctx.needs_input_grad[0]:
-            dx = Fn.conv_input_grad_same(dy, weight, std.view(-1) if std is not None else None)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[3]):
-            xin = Fn.normalize_image(x, mean, std) if mean is not None else x
-            dw, db = Fn.conv_weight_grad(xin, dy, cout, with_bias=has_bias)
-    else:               # the decoder walk (DecoderConvFn.backward): ReLU mask, input grad + border fold, wgrad
-        g = nz(g_act) if want_act else nz(g_pre)
-        g = g.contiguous()
-        if want_act:
-            dy = torch.empty_like(g)
-            check(lib().ast_relu_mask_f32(ptr(g), ptr(mask), ptr(dy), g.numel(), stream_ptr(g.device)), "relu_mask")
-        else:
-            dy = g
-        if ctx.needs_input_grad[0]:
-            dx = Fn.conv_input_grad(dy, weight, upsample, "reflect")
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[3]):
-            dw, db = Fn.conv_weight_grad(x, dy, cout, upsample, "reflect", has_bias)
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[3])
+    if pad_mode == 0:   # the encoder layer; mask = pre
+        dx, dw, db = Fn.encoder_conv_backward(x, weight, mask, mean, std, g_pre, g_act, g_pool, need_x, need_w,
+                                              has_bias)
+    else:               # the decoder layer; mask = the ReLU output (None without ReLU)
+        dx, dw, db = Fn.decoder_conv_backward(x, weight, g_act if want_act else g_pre, mask, upsample, need_x,
+                                              need_w, has_bias)
     return dx, dw, None, db, None, None, None, None, None, None, None, None
 
 
@@ -174,15 +155,7 @@ def _adain_setup(ctx, inputs, output):
 
 def _adain_backward(ctx, g):
     content, style = ctx.saved_tensors
-    n, c, hc, wc = content.shape
-    hs, ws = style.shape[2:]
-    dc = torch.empty_like(content) if ctx.needs_input_grad[0] else None
-    ds = torch.empty_like(style) if ctx.needs_input_grad[1] else None
-    if dc is not None or ds is not None:
-        check(lib().ast_adain_backward_f32(ptr(content), ptr(style), ptr(g.contiguous()), ptr(dc), ptr(ds), n, c, hc,
-                                           wc, hs, ws, float(ctx.alpha), 1 if ctx.swap else 0,
-                                           stream_ptr(content.device)), "adain_backward")
-    return dc, ds, None, None
+    return Fn.adain_backward(content, style, g, ctx.alpha, ctx.swap, *ctx.needs_input_grad[:2]) + (None, None)
 
 
 register_autograd("ast_hip::adain_map", _adain_backward, setup_context=_adain_setup)

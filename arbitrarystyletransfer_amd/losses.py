@@ -3,7 +3,7 @@ tv_loss and the soft-histogram / Earth-Mover loss compu
 (losses.py:8-87; §8f "next" #2), with the SingleDimHistLayer / EarthMoversDistanceLoss modules
 and the module-level `hist` / `earth_movers` instances. Every loss is a torch.ops.ast_hip custom op
 (library.py) whose forward and backward are HIP kernels: one fused launch for the value, one for
-the gradient."""
+the gradient. The registered formula is a loss's only backward: no loss has a Function class."""
 from __future__ import annotations
 
 from . import functional as Fn
@@ -161,11 +161,12 @@ def compute_efdm_loss(t_cs_map, style_map, weight: float = 1.0):
     """The EFDM style loss of one loss tap (Zhang et al., CVPR 2022): weight * mean((f - efdm(f, s))^2)
     with the matched target detached, so the gradient is 2 * weight * (f - target) / numel and none
     reaches the style. The target is Fn.EFDMFn at alpha = 1 under no_grad (the style values, bit for
-    bit), the mean is the sqdiff kernel (Fn.SqDiffMeanFn)."""
+    bit), the mean is the sqdiff kernel (torch.ops.ast_hip.sqdiff_mean, as pixel_mse_loss; the value is
+    an accumulator of its own, not a row of the pool)."""
     x, y = _dev(t_cs_map, "t_cs_map"), _dev(style_map, "style_map")
     with torch.no_grad():
         target = Fn.EFDMFn.apply(x, y, 1.0)
-    return Fn.SqDiffMeanFn.apply(x, target, float(weight))
+    return _ops.sqdiff_mean(x, target, float(weight))
 
 
 def compute_remd_loss(t_cs_map, style_map, weight: float = 1.0):

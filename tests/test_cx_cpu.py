@@ -212,8 +212,7 @@ def test_host_checks_reject_before_launch():
 
 def test_cpu_tensors_and_bad_bandwidths_are_rejected():
     x, y = torch.zeros(1, 8, 2, 2), torch.zeros(1, 8, 2, 2)
-    for call in (lambda: ops.cx_loss(x, y), lambda: ops.cx_center(x, y), lambda: losses.compute_contextual_loss(x, y),
-                 lambda: functional.CxLossFn.apply(x, y, 1.0)):
+    for call in (lambda: ops.cx_loss(x, y), lambda: ops.cx_center(x, y), lambda: losses.compute_contextual_loss(x, y)):
         with pytest.raises(_lib.HipOpError):
             call()
 

@@ -284,12 +284,9 @@ def test_autograd_paths_equal_the_ctypes_path_bitwise(hip_device):
     xg, yg = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
     loss = losses.compute_contextual_loss(xg, yg, 0.7, h)
     (dx,) = torch.autograd.grad(2.0 * loss, xg)
-    fn = functional.CxLossFn.apply(xg, yg, 0.7, h)
-    (dfn,) = torch.autograd.grad(2.0 * fn, xg)
-    bad = [_mismatches(loss.reshape(1), want_loss.reshape(1)), _mismatches(dx, want), _mismatches(fn.reshape(1),
-           want_loss.reshape(1)), _mismatches(dfn, want)]
-    print(f"compute_contextual_loss / CxLossFn vs ops: {bad} mismatches (loss, gradient, loss, gradient)")
-    assert bad == [0, 0, 0, 0]
+    bad = [_mismatches(loss.reshape(1), want_loss.reshape(1)), _mismatches(dx, want)]
+    print(f"compute_contextual_loss vs ops: {bad} mismatches (loss, gradient)")
+    assert bad == [0, 0]
 
 
 @pytest.mark.parametrize("center", [True, False])

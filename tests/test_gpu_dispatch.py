@@ -43,8 +43,10 @@ def test_explain_reports_no_graph_break(hip_device):
 
 
 def test_conv3x3_op_autograd_matches_function_path(hip_device):
-    """ast_hip::conv3x3's registered backward (encoder: zero pad + ReLU/pool taps; decoder:
-    upsample + reflect) vs functional.EncoderConvFn / DecoderConvFn: same kernels, same bits."""
+    """ast_hip::conv3x3's registered backward (encoder: zero pad + ReLU/pool taps, and the conv_1
+    form with the image normalisation; decoder: upsample + reflect, and the form without ReLU) vs
+    functional.EncoderConvFn / DecoderConvFn: both enter the same backward bodies
+    (functional.encoder_conv_backward / decoder_conv_backward), same kernels, same bits."""
     from arbitrarystyletransfer_amd import functional as Fn
     from arbitrarystyletransfer_amd import ops
     d = hip_device
@@ -74,6 +76,41 @@ def test_conv3x3_op_autograd_matches_function_path(hip_device):
             act = Fn.DecoderConvFn.apply(xs, ws, bs, pk, 2, True)
         (act * gd).sum().backward()
         res = (act.detach(), xs.grad, ws.grad, bs.grad)
+        if use_op:
+            op_res = res
+    for a, r in zip(op_res, res):
+        assert torch.equal(a, r)
+    # the decoder form without ReLU: the gradient reaches the weight-gradient kernel unmasked
+    gl = torch.from_numpy(synth.image(46, (2, 48, 24, 20))).to(d) - 0.5
+    for use_op in (True, False):
+        xs, ws, bs = (t.clone().requires_grad_() for t in (x, w, b))
+        if use_op:
+            out, _, _ = torch.ops.ast_hip.conv3x3(xs, ws, pk, bs, 1, 1, None, None, True, False, False, None)
+        else:
+            out = Fn.DecoderConvFn.apply(xs, ws, bs, pk, 1, False)
+        (out * gl).sum().backward()
+        res = (out.detach(), xs.grad, ws.grad, bs.grad)
+        if use_op:
+            op_res = res
+    for a, r in zip(op_res, res):
+        assert torch.equal(a, r)
+    # the conv_1 form: the image normalisation in the gather, its scale in the input gradient, and the
+    # weight gradient on the normalised image
+    x1 = torch.from_numpy(synth.image(47, (2, 3, 24, 20))).to(d)
+    w1 = torch.from_numpy(synth.conv_weight(48, 16, 3, 3)).to(d)
+    b1 = torch.from_numpy(synth.conv_bias(49, 16)).to(d)
+    pk1 = ops.pack_conv3x3(w1)
+    mean = torch.tensor([0.485, 0.456, 0.406], device=d)
+    std = torch.tensor([0.229, 0.224, 0.225], device=d)
+    g1 = torch.from_numpy(synth.image(50, (2, 16, 12, 10))).to(d) - 0.5
+    for use_op in (True, False):
+        xs, ws, bs = (t.clone().requires_grad_() for t in (x1, w1, b1))
+        if use_op:
+            pre, act, pool = torch.ops.ast_hip.conv3x3(xs, ws, pk1, bs, 1, 0, mean, std, True, True, True, None)
+        else:
+            pre, act, pool = Fn.EncoderConvFn.apply(xs, ws, bs, pk1, True, True, mean, std)
+        (pool * g1).sum().backward()
+        res = (pool.detach(), xs.grad, ws.grad, bs.grad)
         if use_op:
             op_res = res
     for a, r in zip(op_res, res):

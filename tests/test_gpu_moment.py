@@ -8,7 +8,6 @@ import torch
 
 import moment_ref as R
 from arbitrarystyletransfer_amd import _lib, losses, ops, synth
-from arbitrarystyletransfer_amd import functional as Fn
 from arbitrarystyletransfer_amd import library  # noqa: F401  (registers the ops)
 
 pytestmark = pytest.mark.gpu
@@ -190,12 +189,6 @@ def test_autograd_paths_equal_the_kernels_bitwise(hip_device):
     c = _case(name)
     x, y_mean, y_cov, loss, state = _forward(name, hip_device, 0.6)
     want = ops.moment_loss_backward(x, state, _one(hip_device, 2.0), 0.6)
-    leaf = x.clone().requires_grad_(True)
-    ym, yc = y_mean.clone().requires_grad_(True), y_cov.clone().requires_grad_(True)
-    out = Fn.MomentLossFn.apply(leaf, ym, yc, 0.6)
-    (2.0 * out).backward()
-    assert _same(out.detach().reshape(1), loss.reshape(1)) and _same(leaf.grad, want)
-    assert ym.grad is None and yc.grad is None                      # the target gets no gradient
     # the registered op: the same kernels, and its fake kernel's shapes
     res = torch.ops.ast_hip.moment_loss(x, y_mean, y_cov, 0.6)
     assert all(_same(a, b) for a, b in zip(res, (loss.reshape(()), state[3], state[0], state[1], state[2])))
@@ -203,8 +196,11 @@ def test_autograd_paths_equal_the_kernels_bitwise(hip_device):
     fake = torch.ops.ast_hip.moment_loss(x.to(m), y_mean.to(m), y_cov.to(m), 0.6)
     assert [(tuple(t.shape), t.dtype) for t in fake] == [(tuple(t.shape), t.dtype) for t in res]
     leaf2 = x.clone().requires_grad_(True)
-    (2.0 * torch.ops.ast_hip.moment_loss(leaf2, y_mean, y_cov, 0.6)[0]).backward()
-    assert _same(leaf2.grad, want)
+    ym, yc = y_mean.clone().requires_grad_(True), y_cov.clone().requires_grad_(True)
+    out = torch.ops.ast_hip.moment_loss(leaf2, ym, yc, 0.6)[0]
+    (2.0 * out).backward()
+    assert _same(out.detach().reshape(1), loss.reshape(1)) and _same(leaf2.grad, want)
+    assert ym.grad is None and yc.grad is None                      # the target gets no gradient
     torch.library.opcheck(torch.ops.ast_hip.moment_loss, (x.clone().requires_grad_(True), y_mean, y_cov, 0.6),
                           test_utils=("test_schema", "test_faketensor", "test_autograd_registration"))
     # losses.compute_moment_loss takes the maps; the style map gets no gradient

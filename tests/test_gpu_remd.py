@@ -183,12 +183,9 @@ def test_autograd_equals_the_backward_kernels_bitwise(hip_device):
     (dx,) = torch.autograd.grad(2.0 * loss, xg)
     want_loss, _, _, br, state = ops.remd_loss(x, y, 0.7)
     want = ops.remd_loss_backward(x, y, state, br, _one(hip_device, 2.0), 0.7)
-    fn = functional.RemdLossFn.apply(xg, yg, 0.7)
-    (dfn,) = torch.autograd.grad(2.0 * fn, xg)
-    bad = [_mismatches(loss.reshape(1), want_loss.reshape(1)), _mismatches(dx, want), _mismatches(fn.reshape(1),
-           want_loss.reshape(1)), _mismatches(dfn, want)]
-    print(f"compute_remd_loss / RemdLossFn vs ops: {bad} mismatches (loss, gradient, loss, gradient)")
-    assert bad == [0, 0, 0, 0]
+    bad = [_mismatches(loss.reshape(1), want_loss.reshape(1)), _mismatches(dx, want)]
+    print(f"compute_remd_loss vs ops: {bad} mismatches (loss, gradient)")
+    assert bad == [0, 0]
 
 
 def test_style_gets_no_gradient(hip_device):
