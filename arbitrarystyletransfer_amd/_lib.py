@@ -169,6 +169,7 @@ SIGNATURES = {
     "ast_adaattn_flash_bwd_q_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ast_adaattn_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "ast_adaattn_fwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _i, _i, _i, _i, _i, _i, _p]),
+    "ast_adaattn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "ast_soft_hist_workspace_floats": (_ll, [_i]),
     "ast_soft_hist_f32": (_i, [_p, _i, _ll, _f, _p, _p, _ll, _p]),
     "ast_emd_loss_f32": (_i, [_p, _p, _i, _f, _p, _p, _p, _p]),

@@ -769,41 +769,66 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 namespace {
 
-struct AttnLayout {  // workspace carve-up (bytes), shared by the size query and the launcher
-  int cp, nqp, nkp, ksplit, kchunk;
-  size_t stats, vmean, q, k, v, v2, part, total;
-};
-
-// bf16 path: split the keys when the query tiles leave the chip underfilled (< 256 workgroups):
-// ~512 workgroups, >= 2 key blocks per split (AST_ATTN_KSPLIT=0: never, for A/B runs)
-void attn_split(int dtype, int n, int nqp, int nkp, int& ksplit, int& kchunk) {
+// Split the keys when the query tiles leave the chip underfilled (wgs < 256 workgroups): ~512
+// workgroups, >= 2 key blocks per split (AST_ATTN_KSPLIT=0: never, for A/B runs)
+void attn_split(int64_t wgs, int nblk, int& ksplit, int& kchunk) {
   static const int on = ast_env::get("AST_ATTN_KSPLIT", 1);
-  const int nblk = nkp / BK;
-  const bool big = dtype != 0 && (int64_t)n * (nqp / 256) >= 512;  // fp32: 128 queries per workgroup
-  const int64_t wgs = (int64_t)n * (nqp / (big ? 256 : 128));
   int ks = 1;
   if (on && wgs < 256 && nblk >= 4) ks = (int)std::min<int64_t>((512 + wgs - 1) / wgs, nblk / 2);
   kchunk = (nblk + ks - 1) / ks;
   ksplit = (nblk + kchunk - 1) / kchunk;  // every split non-empty
 }
 
+// The attention launch, decided in one place: ast_adaattn_plan reports it, attn_layout sizes the
+// split partials from it and ast_adaattn_fwd launches it. nw = waves (of 32 queries) per workgroup:
+// 4 on the fp32 path; bf16 takes 8 (each K/V block staged in LDS then serves 256 queries) once there
+// are >= 512 such workgroups, and 4 below that, to spread a small problem over more CUs.
+struct AttnPlan {
+  int nw, qtiles, ksplit, kchunk, nqp, nkp;
+};
+
+AttnPlan attn_plan(int dtype, int n, int nq, int nk) {
+  AttnPlan P;
+  P.nqp = round_up(nq, dtype == 0 ? 128 : 256);
+  P.nkp = round_up(nk, BK);
+  const bool big = dtype != 0 && (int64_t)n * (P.nqp / 256) >= 512;
+  P.nw = big ? 8 : 4;
+  P.qtiles = P.nqp / (P.nw * 32);
+  attn_split((int64_t)n * P.qtiles, P.nkp / BK, P.ksplit, P.kchunk);
+  return P;
+}
+
+struct AttnLayout {  // workspace carve-up (bytes), shared by the size query and the launcher
+  int cp;
+  AttnPlan plan;
+  size_t stats, vmean, q, k, v, v2, part, total;
+};
+
 AttnLayout attn_layout(int dtype, int n, int c, int nq, int nk) {
   AttnLayout L;
   L.cp = round_up(c, 32);
-  L.nqp = round_up(nq, dtype == 0 ? 128 : 256);
-  L.nkp = round_up(nk, BK);
+  L.plan = attn_plan(dtype, n, nq, nk);
+  const int nqp = L.plan.nqp, nkp = L.plan.nkp, ksplit = L.plan.ksplit;
   const size_t es = dtype == 0 ? 4 : 2;
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
   L.stats = 0;
   L.vmean = al(4 * sizeof(float) * (size_t)n * c);
   L.q = L.vmean + al(sizeof(float) * (size_t)n * c);
-  L.k = L.q + al(es * (size_t)n * L.cp * L.nqp);
-  L.v = L.k + al(es * (size_t)n * L.cp * L.nkp);
-  L.v2 = L.v + al(es * (size_t)n * L.cp * L.nkp);
-  L.part = dtype == 0 ? L.v2 : L.v2 + al(es * (size_t)n * L.cp * L.nkp);
-  attn_split(dtype, n, L.nqp, L.nkp, L.ksplit, L.kchunk);
-  L.total = L.part + (L.ksplit > 1 ? al(sizeof(float) * (size_t)L.ksplit * n * L.nqp * (2 + 2 * (size_t)L.cp)) : 0);
+  L.k = L.q + al(es * (size_t)n * L.cp * nqp);
+  L.v = L.k + al(es * (size_t)n * L.cp * nkp);
+  L.v2 = L.v + al(es * (size_t)n * L.cp * nkp);
+  L.part = dtype == 0 ? L.v2 : L.v2 + al(es * (size_t)n * L.cp * nkp);
+  L.total = L.part + (ksplit > 1 ? al(sizeof(float) * (size_t)ksplit * n * nqp * (2 + 2 * (size_t)L.cp)) : 0);
   return L;
+}
+
+// shape and dtype checks shared by ast_adaattn_fwd and ast_adaattn_plan
+int attn_check(int dtype, int n, int c, int hc, int wc, int hs, int ws) {
+  if (n <= 0 || c <= 0 || hc <= 0 || wc <= 0 || hs <= 0 || ws <= 0) return AST_E_SHAPE;
+  if (dtype != 0 && dtype != 1) return AST_E_UNSUPPORTED;
+  if (c > 128) return AST_E_UNSUPPORTED;
+  if ((int64_t)hc * wc > (1 << 28) || (int64_t)hs * ws > (1 << 28) || (int64_t)n * c > (1 << 28)) return AST_E_SHAPE;
+  return AST_OK;
 }
 
 template <typename K>
@@ -824,15 +849,14 @@ int ast_adaattn_fwd(int dtype, const void* content, const void* style, const flo
                     const float* wv, void* out, void* workspace, size_t workspace_bytes, int n, int c, int hc,
                     int wc, int hs, int ws, void* stream) {
   if (!content || !style || !wq || !wk || !wv || !out || !workspace) return AST_E_NULLPTR;
-  if (n <= 0 || c <= 0 || hc <= 0 || wc <= 0 || hs <= 0 || ws <= 0) return AST_E_SHAPE;
-  if (dtype != 0 && dtype != 1) return AST_E_UNSUPPORTED;
-  if (c > 128) return AST_E_UNSUPPORTED;
-  if ((int64_t)hc * wc > (1 << 28) || (int64_t)hs * ws > (1 << 28) || (int64_t)n * c > (1 << 28)) return AST_E_SHAPE;
+  if (const int bad = attn_check(dtype, n, c, hc, wc, hs, ws)) return bad;
   if (workspace_bytes < ast_adaattn_workspace_bytes(dtype, n, c, hc, wc, hs, ws)) return AST_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int nq = hc * wc, nk = hs * ws;
   const AttnLayout L = attn_layout(dtype, n, c, nq, nk);
-  const int cp = L.cp, nqp = L.nqp, nkp = L.nkp, ct = cp / 32;
+  const AttnPlan& P = L.plan;
+  const int cp = L.cp, nqp = P.nqp, nkp = P.nkp, ct = cp / 32;
+  const int nw = P.nw, qtiles = P.qtiles;
   unsigned char* wsb = (unsigned char*)workspace;
   float* stats = (float*)(wsb + L.stats);
   const dim3 pgrid((unsigned)(round_up(nqp > nkp ? nqp : nkp, 128) / 128), (unsigned)n, 3);
@@ -850,16 +874,15 @@ int ast_adaattn_fwd(int dtype, const void* content, const void* style, const flo
                            : ct == 3 ? project_kernel<float, 3> : project_kernel<float, 4>;
     if ((e = set_lds(proj, plds)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(proj, pgrid, dim3(256), plds, st, pa);
-    const int qtiles = nqp / 128;
-    float* part = L.ksplit > 1 ? (float*)(wsb + L.part) : nullptr;
-    AttnArgs aa{q, k, v, content, stats, out, n, c, cp, nq, nk, nqp, nkp, qtiles, L.ksplit, L.kchunk, part};
+    float* part = P.ksplit > 1 ? (float*)(wsb + L.part) : nullptr;
+    AttnArgs aa{q, k, v, content, stats, out, n, c, cp, nq, nk, nqp, nkp, qtiles, P.ksplit, P.kchunk, part};
     void (*att)(AttnArgs) = ct == 1 ? attend_f32_kernel<float, 1> : ct == 2 ? attend_f32_kernel<float, 2>
                           : ct == 3 ? attend_f32_kernel<float, 3> : attend_f32_kernel<float, 4>;
-    hipLaunchKernelGGL(att, dim3((unsigned)(n * qtiles * L.ksplit)), dim3(256), 0, st, aa);
-    if (L.ksplit > 1) {
+    hipLaunchKernelGGL(att, dim3((unsigned)(n * qtiles * P.ksplit)), dim3(nw * 64), 0, st, aa);
+    if (P.ksplit > 1) {
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
       const int64_t tot = (int64_t)n * c * nq;
-      MergeArgs ma{content, stats, nullptr, out, part, n, c, cp, nq, nqp, L.ksplit};
+      MergeArgs ma{content, stats, nullptr, out, part, n, c, cp, nq, nqp, P.ksplit};
       hipLaunchKernelGGL(attn_merge_kernel<float>, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 8192)), dim3(256),
                          0, st, ma);
     }
@@ -880,29 +903,38 @@ int ast_adaattn_fwd(int dtype, const void* content, const void* style, const flo
   const size_t plds16 = 2 * (size_t)(128 + cp) * (((c + 15) & ~15) + 8);
   if ((e = set_lds(proj, plds16)) != hipSuccess) return (int)e;
   hipLaunchKernelGGL(proj, pgrid, dim3(256), plds16, st, pa);
-  // 8 waves (256 queries) per workgroup: each K/V block staged in LDS serves 256 queries. Small
-  // problems (< 512 such workgroups) use 4-wave workgroups instead, to spread over more CUs.
-  const bool big = (int64_t)n * (nqp / 256) >= 512;
-  const int nw = big ? 8 : 4, qtiles = nqp / (nw * 32);
-  float* part = L.ksplit > 1 ? (float*)(wsb + L.part) : nullptr;
+  float* part = P.ksplit > 1 ? (float*)(wsb + L.part) : nullptr;
   AttnB16Args aa{q, k, v, v2, (const bf16*)content, stats, vmean, (bf16*)out, n, c, cp, nq, nk, nqp, nkp, qtiles,
-                 L.ksplit, L.kchunk, part};
+                 P.ksplit, P.kchunk, part};
   void (*att)(AttnB16Args);
-  if (big)
+  if (nw == 8)
     att = ct == 1 ? attend_bf16_kernel<1, 8> : ct == 2 ? attend_bf16_kernel<2, 8> : ct == 3 ? attend_bf16_kernel<3, 8>
                                                                                     : attend_bf16_kernel<4, 8>;
   else
     att = ct == 1 ? attend_bf16_kernel<1, 4> : ct == 2 ? attend_bf16_kernel<2, 4> : ct == 3 ? attend_bf16_kernel<3, 4>
                                                                                     : attend_bf16_kernel<4, 4>;
-  hipLaunchKernelGGL(att, dim3((unsigned)(n * qtiles * L.ksplit)), dim3(nw * 64), 0, st, aa);
-  if (L.ksplit > 1) {
+  hipLaunchKernelGGL(att, dim3((unsigned)(n * qtiles * P.ksplit)), dim3(nw * 64), 0, st, aa);
+  if (P.ksplit > 1) {
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     const int64_t tot = (int64_t)n * c * nq;
-    MergeArgs ma{content, stats, vmean, out, part, n, c, cp, nq, nqp, L.ksplit};
+    MergeArgs ma{content, stats, vmean, out, part, n, c, cp, nq, nqp, P.ksplit};
     hipLaunchKernelGGL(attn_merge_kernel<bf16>, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 8192)), dim3(256),
                        0, st, ma);
   }
   return (int)hipGetLastError();
+}
+
+int ast_adaattn_plan(int dtype, int n, int c, int hc, int wc, int hs, int ws, int* waves, int* ksplit, int* kchunk,
+                     int* nqp, int* nkp) {
+  if (!waves || !ksplit || !kchunk || !nqp || !nkp) return AST_E_NULLPTR;
+  if (const int bad = attn_check(dtype, n, c, hc, wc, hs, ws)) return bad;
+  const AttnPlan P = attn_plan(dtype, n, hc * wc, hs * ws);
+  *waves = P.nw;
+  *ksplit = P.ksplit;
+  *kchunk = P.kchunk;
+  *nqp = P.nqp;
+  *nkp = P.nkp;
+  return AST_OK;
 }
 
 }  // extern "C"

@@ -1107,6 +1107,14 @@ int ast_adaattn_fwd(int dtype, const void* content, const void* style, const flo
                     const float* wk, const float* wv, void* out, void* workspace,
                     size_t workspace_bytes, int n, int c, int hc, int wc, int hs, int ws,
                     void* stream);
+/* The attention launch ast_adaattn_fwd makes for these sizes (host only; the launcher takes its
+ * launch from the same function, so this is the plan of the call, not a model of it).
+ * waves: queries per workgroup / 32 (4 on the fp32 path; 4 or 8 for bf16). ksplit: parts the keys
+ * are split into (1: no split, no merge kernel); kchunk: 32-key blocks per part. nqp / nkp: the
+ * padded query / key counts of the workspace's Q and K, V. Returns the shape and dtype errors of
+ * ast_adaattn_fwd; AST_E_NULLPTR for a null output pointer. */
+int ast_adaattn_plan(int dtype, int n, int c, int hc, int wc, int hs, int ws, int* waves, int* ksplit,
+                     int* kchunk, int* nqp, int* nkp);
 
 /* ---------------------------------------------------------------------------------------------
  * Remaining train.py loss terms (SURVEY §8f "next" #2). Scalars are added into the loss
