@@ -557,20 +557,23 @@ class AdaINStyleTransfer(nn.Module):
             return f[:b], f[b:]
         return self.encoder(content_img)[0], self.encoder(style_img)[0]
 
-    def _check_preserve_color(self, *imgs):
+    def _inference_only(self, what, *imgs):
         if torch.is_grad_enabled() and (any(i.requires_grad for i in imgs)
                                         or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("preserve_color is inference-only; run it under torch.no_grad()")
+            raise NotImplementedError(f"{what} is inference-only; run it under torch.no_grad()")
 
-    def forward(self, content_img, style_img, alpha: float = 1.0, preserve_color: bool = False):
-        if preserve_color:
-            self._check_preserve_color(content_img, style_img)
-        f_c, f_s = self.encode_pair(content_img, style_img)
-        t = self.adain(f_c, f_s, alpha=alpha)
+    def _decode(self, t, content_img, preserve_color):
+        """The image of the transformed relu4_1 map t; preserve_color: with content_img's colours."""
         out = self.decoder(t)
         if preserve_color:
             return _luma_transfer(out, content_img)
         return out
+
+    def forward(self, content_img, style_img, alpha: float = 1.0, preserve_color: bool = False):
+        if preserve_color:
+            self._inference_only("preserve_color", content_img, style_img)
+        f_c, f_s = self.encode_pair(content_img, style_img)
+        return self._decode(self.adain(f_c, f_s, alpha=alpha), content_img, preserve_color)
 
     def refine(self, content_img, style_img, stylizer, **kw):
         """The feed-forward result polished by optimisation: `stylizer` (strotss.StrotssStylizer) starts
@@ -586,23 +589,13 @@ class AdaINStyleTransfer(nn.Module):
         with. The two images may differ in size (each side at least 24 pixels: a 3x3 relu4_1 map);
         style_img is [N, 3, Hs, Ws] or [1, 3, Hs, Ws]. Inference only; normalize as StyleSwap,
         preserve_color as in forward."""
-        if torch.is_grad_enabled() and (content_img.requires_grad or style_img.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_swap is inference-only; run it under torch.no_grad()")
+        self._inference_only("stylize_swap", content_img, style_img)
         f_c, f_s = self.encode_pair(content_img, style_img)
         if _compiling():
             t = _ops().style_swap(f_c, f_s, float(alpha), bool(normalize))
         else:
             t = ops.style_swap(f_c, f_s, alpha=alpha, normalize=bool(normalize))
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
-
-    def _inference_only(self, what, *imgs):
-        if torch.is_grad_enabled() and (any(i.requires_grad for i in imgs)
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(f"{what} is inference-only; run it under torch.no_grad()")
+        return self._decode(t, content_img, preserve_color)
 
     def auto_labels(self, content_img, style_imgs, auto: AutoRegions = AutoRegions()):
         """The region maps that `labels=auto` gives the regional methods, for content_img [N, 3, H, W]
@@ -631,6 +624,54 @@ class AdaINStyleTransfer(nn.Module):
             raise ValueError("labels=AutoRegions(...) makes style_labels and weights itself: leave both None")
         return labels
 
+    # -- the front end of the four regional methods. A new one plugs in here: _regional_request, its own
+    #    host-side rules, then _regional_inputs (or, without weights, _regional_features), one op, _decode
+    def _regional_request(self, what, content_img, style_imgs, labels, style_labels, weights=None):
+        """What every regional method checks first: (the AutoRegions request or None, N, S)."""
+        self._inference_only(what, content_img, style_imgs)
+        if content_img.dim() != 4 or style_imgs.dim() != 4:
+            raise ValueError(f"{what} needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
+        auto = self._auto_request(labels, style_labels, weights)
+        return auto, int(content_img.shape[0]), int(style_imgs.shape[0])
+
+    def _regional_features(self, content_img, style_imgs, labels, style_labels, auto):
+        """(f_c, f_s, labels, style_labels, weights): both relu4_1 maps, and with an AutoRegions request
+        the label maps and weights it makes from them (otherwise the labels as given, weights None)."""
+        f_c = self.encoder(content_img)[0]
+        f_s = self.encoder(style_imgs)[0]
+        if auto is not None:
+            return (f_c, f_s) + _auto_regions(f_c, f_s, auto)
+        return f_c, f_s, labels, style_labels, None
+
+    def _regional_inputs(self, content_img, style_imgs, labels, style_labels, auto, w):
+        """What the weighted regional methods hand their op, after their own host-side rules: (f_c, f_s,
+        content labels, style labels or None, w). The label maps are at relu4_1 resolution on the maps'
+        device, one region (all 0) when labels is None; w, the [1 or N, K, S] float64 host-side mix of
+        region_weights, is the caller's unless an AutoRegions request makes it here."""
+        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
+        f_c, f_s, labels, style_labels, weights = self._regional_features(content_img, style_imgs, labels,
+                                                                          style_labels, auto)
+        if auto is not None:
+            w = region_weights(weights, n, s)
+        if labels is None:
+            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
+        else:
+            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(f_c.device)
+        sl = None
+        if style_labels is not None:
+            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(f_c.device)
+        return f_c, f_s, lab, sl, w
+
+    def _regional_mix(self, what, content_img, style_imgs, labels, weights, style_labels):
+        """The whole front end of a method whose op mixes the S styles themselves (at most
+        ops.MAX_STYLE_ROWS of them): _regional_inputs with the mix as the op takes it, fp32 on the device."""
+        auto, n, s = self._regional_request(what, content_img, style_imgs, labels, style_labels, weights)
+        if s > ops.MAX_STYLE_ROWS:
+            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
+        w = None if auto is not None else region_weights(weights, n, s, single_region=labels is None)
+        f_c, f_s, lab, sl, w = self._regional_inputs(content_img, style_imgs, labels, style_labels, auto, w)
+        return f_c, f_s, lab, sl, w.float().to(f_c.device)
+
     def stylize_swap_regions(self, content_img, style_imgs, labels=None, style_labels=None, alpha: float = 1.0,
                              normalize: bool = False, preserve_color: bool = False):
         """Guided style swap (ops.style_swap_guided on the relu4_1 maps): content_img [N, 3, H, W]
@@ -646,19 +687,10 @@ class AdaINStyleTransfer(nn.Module):
         from the bank, in the content map it passes the content through.
         style_labels without labels: ValueError. normalize as stylize_swap, preserve_color as forward.
         labels=AutoRegions(...): both maps as auto_labels makes them (style_labels must be None)."""
-        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_swap_regions is inference-only; run it under torch.no_grad()")
-        if content_img.dim() != 4 or style_imgs.dim() != 4:
-            raise ValueError("stylize_swap_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
-        auto = self._auto_request(labels, style_labels)
+        auto, n, s = self._regional_request("stylize_swap_regions", content_img, style_imgs, labels, style_labels)
         if style_labels is not None and labels is None:
             raise ValueError("style_labels without labels: give the content's label map too")
-        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
-        f_c = self.encoder(content_img)[0]
-        f_s = self.encoder(style_imgs)[0]
-        if auto is not None:
-            labels, style_labels, _ = _auto_regions(f_c, f_s, auto)
+        f_c, f_s, labels, style_labels, _ = self._regional_features(content_img, style_imgs, labels, style_labels, auto)
         dev = f_c.device
         if labels is None:
             cc = torch.zeros((n, f_c.shape[2] - 2, f_c.shape[3] - 2), device=dev, dtype=torch.uint8)
@@ -679,10 +711,7 @@ class AdaINStyleTransfer(nn.Module):
             t = _ops().style_swap_guided(f_c, f_s, cc, sc, float(alpha), bool(normalize))
         else:
             t = ops.style_swap_guided(f_c, f_s, cc, sc, alpha=alpha, normalize=bool(normalize))
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
+        return self._decode(t, content_img, preserve_color)
 
     # -- one style, many contents: the style owner encodes the style once and
     #    broadcasts its relu4_1 statistics (dp.broadcast_style_stats, 2*512 floats) --------------
@@ -698,14 +727,10 @@ class AdaINStyleTransfer(nn.Module):
         """Stylise a content batch with given style statistics ([512] shared, or [N, 512]);
         preserve_color as in forward."""
         self._needs_statistics("stylize_with_stats")
-        if torch.is_grad_enabled() and (content_img.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_with_stats is inference-only; run it under torch.no_grad()")
+        self._inference_only("stylize_with_stats", content_img)
         f_c = self.encoder(content_img)[0]
         t = ops.adain_stats(f_c, style_mean, style_std, alpha=alpha, swap_style_stats=not self.adain.canonical)
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
+        return self._decode(t, content_img, preserve_color)
 
     # -- several styles: interpolation and / or one mix of styles per region of the content --------
     def stylize_regions(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
@@ -725,35 +750,17 @@ class AdaINStyleTransfer(nn.Module):
         labels=AutoRegions(...): labels, style_labels and weights as auto_labels makes them from the
         features encoded here (style_labels and weights must be None; K * S <= 64)."""
         self._needs_statistics("stylize_regions")
-        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_regions is inference-only; run it under torch.no_grad()")
-        if content_img.dim() != 4 or style_imgs.dim() != 4:
-            raise ValueError("stylize_regions needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
-        auto = self._auto_request(labels, style_labels, weights)
-        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
-        if auto is None:
-            w = region_weights(weights, n, s, single_region=labels is None)
-            k = int(w.shape[1])
-        else:
-            k = auto.regions
+        auto, n, s = self._regional_request("stylize_regions", content_img, style_imgs, labels, style_labels, weights)
+        w = None if auto is not None else region_weights(weights, n, s, single_region=labels is None)
+        k = auto.regions if auto is not None else int(w.shape[1])
         if s * (k if style_labels is not None or auto is not None else 1) > ops.MAX_STYLE_ROWS:
             raise ValueError(f"at most {ops.MAX_STYLE_ROWS} rows of style statistics (S, or K * S with style_labels)")
-        f_c = self.encoder(content_img)[0]
-        f_s = self.encoder(style_imgs)[0]
-        if auto is not None:
-            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
-            w = region_weights(weights, n, s)
-        if labels is None:
-            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
-        else:
-            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels")
-        if style_labels is None:
+        f_c, f_s, lab, sl, w = self._regional_inputs(content_img, style_imgs, labels, style_labels, auto, w)
+        if sl is None:
             mean, std = channel_stats(f_s)
             mean, std = mean.flatten(1), std.flatten(1)                       # [S, C]
             mix = w
         else:
-            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels")
             rm, rs, _ = ops.region_stats(f_s, sl, k)                          # [S, K, C]
             c = int(f_s.shape[1])
             mean = rm.transpose(0, 1).reshape(k * s, c)                       # row k * S + s
@@ -763,10 +770,7 @@ class AdaINStyleTransfer(nn.Module):
                 mix[:, r, r * s:(r + 1) * s] = w[:, r]
         t = ops.adain_regions(f_c, lab, mean, std, mix.float().to(f_c.device), alpha=alpha,
                               swap_style_stats=not self.adain.canonical)
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
+        return self._decode(t, content_img, preserve_color)
 
     def stylize_regions_wct(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
                             style_labels=None, preserve_color: bool = False, eps_rel: float = ops.WCT_EPS_REL,
@@ -782,38 +786,13 @@ class AdaINStyleTransfer(nn.Module):
         statistics of each style's own region k; where a style of non-zero weight has fewer than 2
         such pixels, the region keeps the content's features. eps_rel and iters as WCT.
         labels=AutoRegions(...) as in stylize_regions."""
-        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_regions_wct is inference-only; run it under torch.no_grad()")
-        if content_img.dim() != 4 or style_imgs.dim() != 4:
-            raise ValueError("stylize_regions_wct needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
-        auto = self._auto_request(labels, style_labels, weights)
-        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
-        if s > ops.MAX_STYLE_ROWS:
-            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
-        if auto is None:
-            w = region_weights(weights, n, s, single_region=labels is None)
-        f_c = self.encoder(content_img)[0]
-        f_s = self.encoder(style_imgs)[0]
-        if auto is not None:
-            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
-            w = region_weights(weights, n, s)
-        if labels is None:
-            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
-        else:
-            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(f_c.device)
-        sl = None
-        if style_labels is not None:
-            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(f_c.device)
-        mix = w.float().to(f_c.device)
+        f_c, f_s, lab, sl, mix = self._regional_mix("stylize_regions_wct", content_img, style_imgs, labels, weights,
+                                                    style_labels)
         if _compiling():
             t = _ops().wct_regions(f_c, lab, f_s, mix, sl, float(alpha), float(eps_rel), int(iters))
         else:
             t = ops.wct_regions(f_c, lab, f_s, mix, style_labels=sl, alpha=alpha, eps_rel=eps_rel, iters=iters)
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
+        return self._decode(t, content_img, preserve_color)
 
     def stylize_regions_efdm(self, content_img, style_imgs, labels=None, weights=None, alpha: float = 1.0,
                              style_labels=None, preserve_color: bool = False):
@@ -829,38 +808,13 @@ class AdaINStyleTransfer(nn.Module):
         values of each style's own region k; where a style of non-zero weight has no such pixel, the
         region keeps the content's features. relu4_1 maps of at most ops.EFDM_FUSED_MAX pixels (a
         1024 x 1024 image). labels=AutoRegions(...) as in stylize_regions."""
-        if torch.is_grad_enabled() and (content_img.requires_grad or style_imgs.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("stylize_regions_efdm is inference-only; run it under torch.no_grad()")
-        if content_img.dim() != 4 or style_imgs.dim() != 4:
-            raise ValueError("stylize_regions_efdm needs content_img [N, 3, H, W] and style_imgs [S, 3, Hs, Ws]")
-        auto = self._auto_request(labels, style_labels, weights)
-        n, s = int(content_img.shape[0]), int(style_imgs.shape[0])
-        if s > ops.MAX_STYLE_ROWS:
-            raise ValueError(f"at most {ops.MAX_STYLE_ROWS} styles, got {s}")
-        if auto is None:
-            w = region_weights(weights, n, s, single_region=labels is None)
-        f_c = self.encoder(content_img)[0]
-        f_s = self.encoder(style_imgs)[0]
-        if auto is not None:
-            labels, style_labels, weights = _auto_regions(f_c, f_s, auto)
-            w = region_weights(weights, n, s)
-        if labels is None:
-            lab = torch.zeros((n,) + tuple(f_c.shape[2:]), device=f_c.device, dtype=torch.uint8)
-        else:
-            lab = _feature_labels(labels, n, content_img.shape[2:], f_c.shape[2:], "labels").to(f_c.device)
-        sl = None
-        if style_labels is not None:
-            sl = _feature_labels(style_labels, s, style_imgs.shape[2:], f_s.shape[2:], "style_labels").to(f_c.device)
-        mix = w.float().to(f_c.device)
+        f_c, f_s, lab, sl, mix = self._regional_mix("stylize_regions_efdm", content_img, style_imgs, labels, weights,
+                                                    style_labels)
         if _compiling():
             t = _ops().efdm_regions(f_c, lab, f_s, mix, sl, float(alpha))
         else:
             t = ops.efdm_regions(f_c, lab, f_s, mix, style_labels=sl, alpha=alpha)
-        out = self.decoder(t)
-        if preserve_color:
-            return _luma_transfer(out, content_img)
-        return out
+        return self._decode(t, content_img, preserve_color)
 
 
 def region_weights(weights, n: int, s: int, single_region: bool = False):

@@ -67,14 +67,56 @@ def _timed(tag, flops, device, launch):
     return code
 
 
-def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
+# ------------------------------------------------------------------------------------------------
+# Argument checks shared by the ops. A new op composes these and adds only its own limits after them:
+# _dev / _dev_typed (the device gate: every tensor argument passes it first), _pair (two NCHW maps),
+# _map_and_labels / _labels (a map and its uint8 label map), _style_bank (the bank, mix and labels of a
+# regional transform) and _like (a tensor that must look like one the library made: state, index, out).
+# ------------------------------------------------------------------------------------------------
+
+def _dev_typed(t: torch.Tensor, name: str, dtype: torch.dtype) -> torch.Tensor:
+    """The device gate: t, a `dtype` tensor on a HIP device, made contiguous."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
     if t.device.type != "cuda":
         raise HipOpError(f"{name} is on {t.device}; arbitrarystyletransfer_amd runs on MI355X (HIP) devices only")
-    if t.dtype != torch.float32:
-        raise HipOpError(f"{name} must be float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise HipOpError(f"{name} must be {dtype}, got {t.dtype}")
     return t.contiguous()
+
+
+def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _dev_typed(t, name, torch.float32)
+
+
+def _like(t, device, dtype, what: str, shape=None, numel=None, msg=None) -> torch.Tensor:
+    """t, which must be a `dtype` tensor on `device` of the given shape (or, with shape None, of `numel`
+    elements), made contiguous. msg replaces the message where several tensors share one."""
+    if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype
+            or (tuple(t.shape) != tuple(shape) if shape is not None else t.numel() != numel)):
+        size = tuple(shape) if shape is not None else f"of {numel} elements"
+        raise HipOpError(msg or f"{what} must be a {dtype} tensor {size} on {device}")
+    return t.contiguous()
+
+
+def _pair(a: torch.Tensor, b: torch.Tensor, na: str, nb: str, what: str, batch: bool = True, side: int = 1,
+          named: bool = True):
+    """Two fp32 NCHW maps on one device, not empty, with equal C; batch: b's batch is a's or 1; side: the
+    least height and width (3 where 3x3 patches are taken); named: the message names the two shapes.
+    (a, b, n, nb, c, ha, wa, hb, wb)."""
+    a, b = _dev(a, na), _dev(b, nb)
+    if (a.dim() != 4 or b.dim() != 4 or a.shape[1] != b.shape[1] or (batch and b.shape[0] not in (1, a.shape[0]))
+            or a.numel() == 0 or b.numel() == 0 or min(a.shape[2:]) < side or min(b.shape[2:]) < side):
+        needs = ["equal C"] + ([f"sides of at least {side}"] if side > 1 else []) + (
+            ["a style batch of N or 1"] if batch else [])
+        needs = " and ".join(filter(None, [", ".join(needs[:-1]), needs[-1]]))
+        la, lb = (f"{na} ", f"{nb} ") if named else ("", "")
+        raise HipOpError(f"{what} needs non-empty NCHW maps with {needs}: "
+                         f"{la}{tuple(a.shape)} vs {lb}{tuple(b.shape)}")
+    if a.device != b.device:
+        raise HipOpError(f"{nb} is on {b.device}, {na} on {a.device}")
+    n, c, ha, wa = (int(s) for s in a.shape)
+    return a, b, n, int(b.shape[0]), c, ha, wa, int(b.shape[2]), int(b.shape[3])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -290,25 +332,21 @@ def adain_stats(content: torch.Tensor, style_mean: torch.Tensor, style_std: torc
     return out
 
 
-def _dev_typed(t: torch.Tensor, name: str, dtype: torch.dtype) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor")
-    if t.device.type != "cuda":
-        raise HipOpError(f"{name} is on {t.device}; arbitrarystyletransfer_amd runs on MI355X (HIP) devices only")
-    if t.dtype != dtype:
-        raise HipOpError(f"{name} must be {dtype}, got {t.dtype}")
-    return t.contiguous()
-
-
 # Regional multi-style AdaIN (csrc/adain_regions.hip): AST_MAX_REGIONS / AST_MAX_STYLE_ROWS of ast_hip.h
 MAX_REGIONS = 8
 MAX_STYLE_ROWS = 64
 
 
-def _labels(t: torch.Tensor, name: str) -> torch.Tensor:
+def _uint8_first(t, name: str):
+    """A label map of another dtype hears about its dtype before its device (a host-side int map is the
+    usual mistake), and in _map_and_labels before anything about the map it goes with."""
     if isinstance(t, torch.Tensor) and t.dtype != torch.uint8:
         raise HipOpError(f"{name} must be uint8, got {t.dtype}")
-    t = _dev_typed(t, name, torch.uint8)
+    return t
+
+
+def _labels(t: torch.Tensor, name: str, dtype_checked: bool = False) -> torch.Tensor:
+    t = _dev_typed(t if dtype_checked else _uint8_first(t, name), name, torch.uint8)
     if t.dim() != 3 or t.numel() == 0:
         raise HipOpError(f"{name} must be a non-empty [N, H, W] uint8 map, got {tuple(t.shape)}")
     return t
@@ -335,10 +373,9 @@ def resize_labels(labels: torch.Tensor, h: int, w: int):
 
 
 def _map_and_labels(x, labels, what):
-    if isinstance(labels, torch.Tensor) and labels.dtype != torch.uint8:
-        raise HipOpError(f"labels must be uint8, got {labels.dtype}")
+    labels = _uint8_first(labels, "labels")
     x = _dev(x, what)
-    labels = _labels(labels, "labels")
+    labels = _labels(labels, "labels", dtype_checked=True)
     if x.dim() != 4 or x.numel() == 0:
         raise HipOpError(f"{what} must be a non-empty NCHW map, got {tuple(x.shape)}")
     n, c, h, w = (int(s) for s in x.shape)
@@ -410,16 +447,7 @@ def efdm(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, _chunk:
     every output is a copy of a style value; otherwise c + alpha * (t - c).
     content [N, C, Hc, Wc]; style [N, C, Hs, Ws] or [1, C, Hs, Ws] (shared by the batch).
     _chunk (tests): a power of two >= 64 forces the chunk-sort + merge path with that LDS chunk."""
-    content = _dev(content, "content_map")
-    style = _dev(style, "style_map")
-    if (content.dim() != 4 or style.dim() != 4 or content.shape[1] != style.shape[1]
-            or style.shape[0] not in (1, content.shape[0]) or content.numel() == 0 or style.numel() == 0):
-        raise HipOpError(f"EFDM needs non-empty NCHW maps with equal C and a style batch of N or 1: "
-                         f"{tuple(content.shape)} vs {tuple(style.shape)}")
-    if style.device != content.device:
-        raise HipOpError(f"style_map is on {style.device}, content_map on {content.device}")
-    n, c, hc, wc = (int(s) for s in content.shape)
-    ns, hs, ws = int(style.shape[0]), int(style.shape[2]), int(style.shape[3])
+    content, style, n, ns, c, hc, wc, hs, ws = _pair(content, style, "content_map", "style_map", "EFDM", named=False)
     L = lib()
     nbytes = int(L.ast_efdm_ex_workspace_bytes(n, ns, c, hc * wc, hs * ws, int(_chunk)))
     wsb = _ws_bytes(nbytes, "efdm workspace", content.device)
@@ -510,16 +538,7 @@ def wct(content: torch.Tensor, style: torch.Tensor, alpha: float = 1.0, eps_rel:
     the cross-channel covariance: out = alpha * (T (c - mu_c) + mu_s) + (1 - alpha) * c with
     T = cov_s^(1/2) cov_c^(-1/2) (wct_cov, wct_sqrt). content [N, C, Hc, Wc]; style [N, C, Hs, Ws] or
     [1, C, Hs, Ws] (shared by the batch); C <= 1024, at least 2 pixels per map, eps_rel in [1e-4, 1]."""
-    content = _dev(content, "content_map")
-    style = _dev(style, "style_map")
-    if (content.dim() != 4 or style.dim() != 4 or content.shape[1] != style.shape[1]
-            or style.shape[0] not in (1, content.shape[0]) or content.numel() == 0 or style.numel() == 0):
-        raise HipOpError(f"WCT needs non-empty NCHW maps with equal C and a style batch of N or 1: "
-                         f"{tuple(content.shape)} vs {tuple(style.shape)}")
-    if style.device != content.device:
-        raise HipOpError(f"style_map is on {style.device}, content_map on {content.device}")
-    n, c, hc, wc = (int(s) for s in content.shape)
-    ns, hs, ws = int(style.shape[0]), int(style.shape[2]), int(style.shape[3])
+    content, style, n, ns, c, hc, wc, hs, ws = _pair(content, style, "content_map", "style_map", "WCT", named=False)
     L = lib()
     nbytes = int(L.ast_wct_workspace_bytes(n, ns, c, hc * wc, hs * ws))
     wsb = _ws_bytes(nbytes, "wct workspace", content.device)
@@ -542,6 +561,23 @@ def _region_mix(mix, n: int, s: int, device, what: str):
         raise HipOpError(f"{what}: mix must be [N={n} or 1, K <= {MAX_REGIONS}, S={s}] on {device}, got "
                          f"{tuple(mix.shape)} on {mix.device}")
     return mix, int(mix.shape[1])
+
+
+def _style_bank(styles, mix, style_labels, n: int, c: int, device, what: str):
+    """The style side of a regional transform: the fp32 bank [S, C, Hs, Ws], the mix (_region_mix) and the
+    bank's own labels uint8 [S, Hs, Ws] or None, all on `device`: (styles, S, Hs, Ws, mix, K, style_labels)."""
+    styles = _dev(styles, "styles")
+    if styles.dim() != 4 or styles.numel() == 0 or styles.shape[1] != c or styles.device != device:
+        raise HipOpError(f"{what} needs a non-empty style bank [S, C={c}, Hs, Ws] on {device}, got "
+                         f"{tuple(styles.shape)} on {styles.device}")
+    s, hs, ws = int(styles.shape[0]), int(styles.shape[2]), int(styles.shape[3])
+    mix, k = _region_mix(mix, n, s, device, what)
+    if style_labels is not None:
+        style_labels = _labels(style_labels, "style_labels")
+        if tuple(style_labels.shape) != (s, hs, ws) or style_labels.device != device:
+            raise HipOpError(f"style_labels must be [S, Hs, Ws] = {(s, hs, ws)} on {device}, got "
+                             f"{tuple(style_labels.shape)} on {style_labels.device}")
+    return styles, s, hs, ws, mix, k, style_labels
 
 
 def wct_region_cov(x: torch.Tensor, labels: torch.Tensor, regions: int, eps_rel: float = WCT_EPS_REL):
@@ -613,17 +649,8 @@ def wct_regions(content: torch.Tensor, labels: torch.Tensor, styles: torch.Tenso
     for bit. mix is [K, S], [1, K, S] or [N, K, S] on the device, rows summing to 1; a style of weight
     exactly 0 is never read. alpha, eps_rel and iters as wct."""
     content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
-    styles = _dev(styles, "styles")
-    if styles.dim() != 4 or styles.numel() == 0 or styles.shape[1] != c or styles.device != content.device:
-        raise HipOpError(f"wct_regions needs a non-empty style bank [S, C={c}, Hs, Ws] on {content.device}, got "
-                         f"{tuple(styles.shape)} on {styles.device}")
-    s, hs, ws = int(styles.shape[0]), int(styles.shape[2]), int(styles.shape[3])
-    mix, k = _region_mix(mix, n, s, content.device, "wct_regions")
-    if style_labels is not None:
-        style_labels = _labels(style_labels, "style_labels")
-        if tuple(style_labels.shape) != (s, hs, ws) or style_labels.device != content.device:
-            raise HipOpError(f"style_labels must be [S, Hs, Ws] = {(s, hs, ws)} on {content.device}, got "
-                             f"{tuple(style_labels.shape)} on {style_labels.device}")
+    styles, s, hs, ws, mix, k, style_labels = _style_bank(styles, mix, style_labels, n, c, content.device,
+                                                          "wct_regions")
     L = lib()
     nbytes = int(L.ast_wct_regions_workspace_bytes(n, c, h, w, k, s, hs, ws, 0 if style_labels is None else 1))
     wsb = _ws_bytes(nbytes, "wct_regions workspace", content.device)
@@ -673,17 +700,8 @@ def efdm_regions(content: torch.Tensor, labels: torch.Tensor, styles: torch.Tens
     exactly 0 is never used, and a one-hot row copies style values (no arithmetic at alpha == 1).
     alpha as efdm. Planes of at most EFDM_FUSED_MAX elements."""
     content, labels, n, c, h, w = _map_and_labels(content, labels, "content_map")
-    styles = _dev(styles, "styles")
-    if styles.dim() != 4 or styles.numel() == 0 or styles.shape[1] != c or styles.device != content.device:
-        raise HipOpError(f"efdm_regions needs a non-empty style bank [S, C={c}, Hs, Ws] on {content.device}, got "
-                         f"{tuple(styles.shape)} on {styles.device}")
-    s, hs, ws = int(styles.shape[0]), int(styles.shape[2]), int(styles.shape[3])
-    mix, k = _region_mix(mix, n, s, content.device, "efdm_regions")
-    if style_labels is not None:
-        style_labels = _labels(style_labels, "style_labels")
-        if tuple(style_labels.shape) != (s, hs, ws) or style_labels.device != content.device:
-            raise HipOpError(f"style_labels must be [S, Hs, Ws] = {(s, hs, ws)} on {content.device}, got "
-                             f"{tuple(style_labels.shape)} on {style_labels.device}")
+    styles, s, hs, ws, mix, k, style_labels = _style_bank(styles, mix, style_labels, n, c, content.device,
+                                                          "efdm_regions")
     L = lib()
     nbytes = int(L.ast_efdm_regions_workspace_bytes(n, c, h, w, k, s, hs, ws))
     wsb = _ws_bytes(nbytes, "efdm_regions workspace", content.device)
@@ -702,15 +720,7 @@ SWAP_MAX_C = 1024
 def _swap_pair(a: torch.Tensor, b: torch.Tensor, na: str, nb: str, what: str):
     """Two fp32 device NCHW maps with equal C, sides of at least 3 and b's batch equal to a's or 1:
     (a, b, n, ns, c, ha, wa, hb, wb)."""
-    a, b = _dev(a, na), _dev(b, nb)
-    if (a.dim() != 4 or b.dim() != 4 or a.shape[1] != b.shape[1] or b.shape[0] not in (1, a.shape[0])
-            or a.numel() == 0 or b.numel() == 0 or min(a.shape[2:]) < 3 or min(b.shape[2:]) < 3):
-        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C, sides of at least 3 and a style batch of N "
-                         f"or 1: {na} {tuple(a.shape)} vs {nb} {tuple(b.shape)}")
-    if a.device != b.device:
-        raise HipOpError(f"{nb} is on {b.device}, {na} on {a.device}")
-    n, c, ha, wa = (int(s) for s in a.shape)
-    return a, b, n, int(b.shape[0]), c, ha, wa, int(b.shape[2]), int(b.shape[3])
+    return _pair(a, b, na, nb, what, side=3)
 
 
 def patch_match(content_key: torch.Tensor, style_key: torch.Tensor, return_score: bool = False, _splits: int = 0):
@@ -741,10 +751,8 @@ def patch_gather(style_value: torch.Tensor, index: torch.Tensor, content: torch.
     up-to-nine content patches covering (y, x), of the style_value pixel that the patch's match
     (index [N, H - 2, W - 2] int32, as patch_match returns) puts there. One launch."""
     c_, sv, n, ns, c, hc, wc, hs, ws = _swap_pair(content, style_value, "content_map", "style_value", "patch_gather")
-    if (not isinstance(index, torch.Tensor) or index.device != c_.device or index.dtype != torch.int32
-            or tuple(index.shape) != (n, hc - 2, wc - 2)):
-        raise HipOpError(f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
-    index = index.contiguous()
+    index = _like(index, c_.device, torch.int32, "index", shape=(n, hc - 2, wc - 2),
+                  msg=f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
     out = torch.empty_like(c_)
     check(_timed(f"patch_gather {c}ch {hc}x{wc}", -4 * 11 * c_.numel(), c_.device, lambda: lib().ast_patch_gather_f32(
         ptr(sv), ptr(index), ptr(c_), ptr(out), n, ns, c, hc, wc, hs, ws, float(alpha), stream_ptr(c_.device))),
@@ -782,19 +790,12 @@ REMD_ROW, REMD_COL = 1, 2   # the values of `branch`
 def _remd_pair(x: torch.Tensor, y: torch.Tensor, what: str):
     """Two fp32 device NCHW maps with equal C and y's batch equal to x's or 1, inside the limits of
     csrc/remd.hip: (x, y, n, ns, c, m, p) with m, p the pixel counts."""
-    x, y = _dev(x, "x"), _dev(y, "y")
-    if (x.dim() != 4 or y.dim() != 4 or x.shape[1] != y.shape[1] or y.shape[0] not in (1, x.shape[0])
-            or x.numel() == 0 or y.numel() == 0):
-        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C and a style batch of N or 1: "
-                         f"x {tuple(x.shape)} vs y {tuple(y.shape)}")
-    if x.device != y.device:
-        raise HipOpError(f"y is on {y.device}, x on {x.device}")
-    n, c = int(x.shape[0]), int(x.shape[1])
-    m, p = int(x.shape[2] * x.shape[3]), int(y.shape[2] * y.shape[3])
+    x, y, n, ns, c, h, w, hs, ws = _pair(x, y, "x", "y", what)
+    m, p = h * w, hs * ws
     if c > REMD_MAX_C or max(m, p) > REMD_MAX_PIXELS or n > 65535:
         raise HipOpError(f"{what}: C is at most {REMD_MAX_C}, a map has at most {REMD_MAX_PIXELS} pixels and a batch "
                          f"65535 samples: x {tuple(x.shape)} vs y {tuple(y.shape)}")
-    return x, y, n, int(y.shape[0]), c, m, p
+    return x, y, n, ns, c, m, p
 
 
 def cosine_norms(x: torch.Tensor) -> torch.Tensor:
@@ -889,11 +890,9 @@ def remd_loss_backward(x: torch.Tensor, y: torch.Tensor, state, branch: torch.Te
     want = ((u, n * m, torch.float32), (v, ns * p, torch.float32), (rmin, n * m, torch.float32),
             (ridx, n * m, torch.int32), (cmin, n * p, torch.float32), (cidx, n * p, torch.int32),
             (branch, n, torch.uint8), (grad, 1, torch.float32))
-    for t, numel, dt in want:
-        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or t.numel() != numel:
-            raise HipOpError("remd_loss_backward needs the state and branch of remd_loss on x's shapes and a "
-                             "float32 device scalar grad")
-    u, v, rmin, ridx, cmin, cidx, branch, grad = (t.contiguous() for t, _, _ in want)
+    msg = "remd_loss_backward needs the state and branch of remd_loss on x's shapes and a float32 device scalar grad"
+    u, v, rmin, ridx, cmin, cidx, branch, grad = [_like(t, dev, dt, "state", numel=numel, msg=msg)
+                                                  for t, numel, dt in want]
     L = lib()
     nb = int(L.ast_remd_loss_backward_workspace_bytes(n, m, p))
     wsb = _ws_bytes(nb, "remd_loss_backward workspace", dev)
@@ -922,12 +921,6 @@ def _selfsim_pair(x: torch.Tensor, c: torch.Tensor, what: str):
     return x, c, n, ch, m
 
 
-def _selfsim_like(t, x: torch.Tensor, shape, dtype, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise HipOpError(f"{what} must be a {dtype} tensor {tuple(shape)} on {x.device}")
-    return t.contiguous()
-
-
 def _selfsim_planes(x: torch.Tensor):
     n, _, h, w = x.shape
     return (n, h * w, (h * w + 63) // 64)
@@ -938,7 +931,7 @@ def selfsim_colsum(x: torch.Tensor, inv_norm: torch.Tensor) -> torch.Tensor:
     between pixels of x [N, C, H, W], from inv_norm = cosine_norms(x); computed as (HW - 1) - (<xh_j, S> -
     ||xh_j||^2) with S the sum of the unit vectors: no pass over pairs."""
     x, _, n, ch, m = _selfsim_pair(x, x, "selfsim_colsum")
-    u = _selfsim_like(inv_norm, x, (n,) + tuple(x.shape[2:]), torch.float32, "selfsim_colsum: inv_norm")
+    u = _like(inv_norm, x.device, torch.float32, "selfsim_colsum: inv_norm", shape=(n,) + tuple(x.shape[2:]))
     L, dev = lib(), x.device
     nb = int(L.ast_selfsim_colsum_workspace_bytes(n, ch))
     wsb = _ws_bytes(nb, "selfsim_colsum workspace", dev)
@@ -955,7 +948,7 @@ def selfsim_pairs(x: torch.Tensor, c: torch.Tensor, inv_x: torch.Tensor, inv_c: 
     sign(e(k, j)) D_x(k, j), and bit k of word (i, J) of pos / neg is set where e(i, 64 J + k) > 0 / < 0."""
     x, c, n, ch, m = _selfsim_pair(x, c, "selfsim_pairs")
     shp = (n,) + tuple(x.shape[2:])
-    u, v, rx, rc = (_selfsim_like(t, x, shp, torch.float32, f"selfsim_pairs: {k}")
+    u, v, rx, rc = (_like(t, x.device, torch.float32, f"selfsim_pairs: {k}", shape=shp)
                     for t, k in ((inv_x, "inv_x"), (inv_c, "inv_c"), (r_x, "r_x"), (r_c, "r_c")))
     L, dev = lib(), x.device
     nb = int(L.ast_selfsim_pairs_workspace_bytes(n, m))
@@ -1012,17 +1005,16 @@ def selfsim_loss_backward(x: torch.Tensor, state, grad: torch.Tensor, weight: fl
     x, _, n, ch, m = _selfsim_pair(x, x, "selfsim_loss_backward")
     if not isinstance(state, (tuple, list)) or len(state) != 7:
         raise HipOpError("selfsim_loss_backward needs the state (inv_x, inv_c, r_x, r_c, t, pos, neg) of selfsim_loss")
-    shp, pshape = (n,) + tuple(x.shape[2:]), _selfsim_planes(x)
+    shp, pshape, dev = (n,) + tuple(x.shape[2:]), _selfsim_planes(x), x.device
     what = "selfsim_loss_backward: {}"
-    u = _selfsim_like(state[0], x, shp, torch.float32, what.format("inv_x"))
-    rx = _selfsim_like(state[2], x, shp, torch.float32, what.format("r_x"))
-    t = _selfsim_like(state[4], x, shp, torch.float32, what.format("t"))
-    pos = _selfsim_like(state[5], x, pshape, torch.int64, what.format("pos"))
-    neg = _selfsim_like(state[6], x, pshape, torch.int64, what.format("neg"))
-    if not isinstance(grad, torch.Tensor) or grad.device != x.device or grad.dtype != torch.float32 or grad.numel() != 1:
-        raise HipOpError("selfsim_loss_backward needs a float32 device scalar grad")
-    grad = grad.contiguous()
-    L, dev = lib(), x.device
+    u = _like(state[0], dev, torch.float32, what.format("inv_x"), shape=shp)
+    rx = _like(state[2], dev, torch.float32, what.format("r_x"), shape=shp)
+    t = _like(state[4], dev, torch.float32, what.format("t"), shape=shp)
+    pos = _like(state[5], dev, torch.int64, what.format("pos"), shape=pshape)
+    neg = _like(state[6], dev, torch.int64, what.format("neg"), shape=pshape)
+    grad = _like(grad, dev, torch.float32, "grad", numel=1,
+                 msg="selfsim_loss_backward needs a float32 device scalar grad")
+    L = lib()
     nb = int(L.ast_selfsim_loss_backward_workspace_bytes(n, ch, m))
     wsb = _ws_bytes(nb, "selfsim_loss_backward workspace", dev)
     dx = torch.empty_like(x)
@@ -1052,12 +1044,6 @@ def _cx_pair(x: torch.Tensor, y: torch.Tensor, what: str, h: float = 0.5):
     return x, y, n, ns, c, m, p
 
 
-def _cx_like(t, dev, numel: int, dtype, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.numel() != numel:
-        raise HipOpError(f"{what} must be a {dtype} tensor of {numel} elements on {dev}")
-    return t.contiguous()
-
-
 def cx_center(x: torch.Tensor, y: torch.Tensor):
     """(mu [Ns, C], xc, yc): the channel means of y [N or 1, C, Hs, Ws] over its pixels, summed in a fixed
     order, and both maps with them subtracted: the centring of the contextual loss."""
@@ -1071,8 +1057,8 @@ def cx_center(x: torch.Tensor, y: torch.Tensor):
 
 def _cx_rows(x, y, inv_x, inv_y, row_min, what, n, ns, m, p):
     dev, f = x.device, torch.float32
-    return (_cx_like(inv_x, dev, n * m, f, f"{what}: inv_x"), _cx_like(inv_y, dev, ns * p, f, f"{what}: inv_y"),
-            _cx_like(row_min, dev, n * m, f, f"{what}: row_min"))
+    return (_like(inv_x, dev, f, f"{what}: inv_x", numel=n * m), _like(inv_y, dev, f, f"{what}: inv_y", numel=ns * p),
+            _like(row_min, dev, f, f"{what}: row_min", numel=n * m))
 
 
 def cx_rowsum(xc: torch.Tensor, yc: torch.Tensor, inv_x: torch.Tensor, inv_y: torch.Tensor, row_min: torch.Tensor,
@@ -1100,7 +1086,7 @@ def cx_colmax(xc: torch.Tensor, yc: torch.Tensor, inv_x: torch.Tensor, inv_y: to
     _splits."""
     x, y, n, ns, c, m, p = _cx_pair(xc, yc, "cx_colmax", h)
     u, v, r = _cx_rows(x, y, inv_x, inv_y, row_min, "cx_colmax", n, ns, m, p)
-    S = _cx_like(row_sum, x.device, n * m, torch.float32, "cx_colmax: row_sum")
+    S = _like(row_sum, x.device, torch.float32, "cx_colmax: row_sum", numel=n * m)
     L, dev = lib(), x.device
     nb = int(L.ast_cx_colmax_workspace_bytes(n, ns, m, p))
     wsb = _ws_bytes(nb, "cx_colmax workspace", dev)
@@ -1172,18 +1158,18 @@ def cx_loss_backward(x: torch.Tensor, y: torch.Tensor, state, grad: torch.Tensor
     xc, yc = state[0], state[1]
     if isinstance(xc, torch.Tensor) and xc.numel() == 0 and isinstance(yc, torch.Tensor) and yc.numel() == 0:
         xc, yc = x, y   # center was off
-    xc = _cx_like(xc, dev, x.numel(), f, what.format("xc"))
-    yc = _cx_like(yc, dev, y.numel(), f, what.format("yc"))
-    u = _cx_like(state[2], dev, n * m, f, what.format("inv_x"))
-    v = _cx_like(state[3], dev, ns * p, f, what.format("inv_y"))
-    rmin = _cx_like(state[4], dev, n * m, f, what.format("row_min"))
-    ridx = _cx_like(state[5], dev, n * m, torch.int32, what.format("row_index"))
-    S = _cx_like(state[6], dev, n * m, f, what.format("row_sum"))
-    E = _cx_like(state[7], dev, n * m, f, what.format("row_dsum"))
-    cidx = _cx_like(state[9], dev, n * p, torch.int32, what.format("col_index"))
-    cdist = _cx_like(state[10], dev, n * p, f, what.format("col_dist"))
-    cxb = _cx_like(state[11], dev, n, f, what.format("per_sample_cx"))
-    grad = _cx_like(grad, dev, 1, f, what.format("grad"))
+    xc = _like(xc, dev, f, what.format("xc"), numel=x.numel())
+    yc = _like(yc, dev, f, what.format("yc"), numel=y.numel())
+    u = _like(state[2], dev, f, what.format("inv_x"), numel=n * m)
+    v = _like(state[3], dev, f, what.format("inv_y"), numel=ns * p)
+    rmin = _like(state[4], dev, f, what.format("row_min"), numel=n * m)
+    ridx = _like(state[5], dev, torch.int32, what.format("row_index"), numel=n * m)
+    S = _like(state[6], dev, f, what.format("row_sum"), numel=n * m)
+    E = _like(state[7], dev, f, what.format("row_dsum"), numel=n * m)
+    cidx = _like(state[9], dev, torch.int32, what.format("col_index"), numel=n * p)
+    cdist = _like(state[10], dev, f, what.format("col_dist"), numel=n * p)
+    cxb = _like(state[11], dev, f, what.format("per_sample_cx"), numel=n)
+    grad = _like(grad, dev, f, what.format("grad"), numel=1)
     L = lib()
     nb = int(L.ast_cx_loss_backward_workspace_bytes(n, c, m, p))
     wsb = _ws_bytes(nb, "cx_loss_backward workspace", dev)
@@ -1210,12 +1196,6 @@ def _moment_map(x: torch.Tensor, name: str, what: str):
         raise HipOpError(f"{what}: C is at most {MOMENT_MAX_C}, a map has at least 2 pixels and a batch at most "
                          f"32767 samples: {name} {tuple(x.shape)}")
     return x, n, c, m
-
-
-def _moment_like(t, dev, shape, dtype, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise HipOpError(f"{what} must be a {dtype} tensor {tuple(shape)} on {dev}")
-    return t.contiguous()
 
 
 def moment_stats(y: torch.Tensor, _splits: int = 0):
@@ -1248,8 +1228,8 @@ def moment_loss(x: torch.Tensor, y_mean: torch.Tensor, y_cov: torch.Tensor, weig
         raise HipOpError(f"moment_loss: y_mean must be [N or 1, {c}], got "
                          f"{tuple(y_mean.shape) if isinstance(y_mean, torch.Tensor) else y_mean!r}")
     ns = int(y_mean.shape[0])
-    y_mean = _moment_like(y_mean, dev, (ns, c), torch.float32, "moment_loss: y_mean")
-    y_cov = _moment_like(y_cov, dev, (ns, c, c), torch.float32, "moment_loss: y_cov")
+    y_mean = _like(y_mean, dev, torch.float32, "moment_loss: y_mean", shape=(ns, c))
+    y_cov = _like(y_cov, dev, torch.float32, "moment_loss: y_cov", shape=(ns, c, c))
     nb = int(L.ast_moment_loss_workspace_bytes(n, c, m, int(_splits)))
     wsb = _ws_bytes(nb, "moment_loss workspace", dev)
     mean_x = torch.empty((n, c), device=dev, dtype=torch.float32)
@@ -1273,16 +1253,16 @@ def moment_loss_backward(x: torch.Tensor, state, grad: torch.Tensor = None, weig
     if not isinstance(state, (tuple, list)) or len(state) < 3:
         raise HipOpError("moment_loss_backward needs the state of moment_loss")
     dev, what = x.device, "moment_loss_backward: {}"
-    mean_x = _moment_like(state[0], dev, (n, c), torch.float32, what.format("mean_x"))
-    sign_mu = _moment_like(state[1], dev, (n, c), torch.int8, what.format("sign_mu"))
-    sign_cov = _moment_like(state[2], dev, (n, c, c), torch.int8, what.format("sign_cov"))
+    mean_x = _like(state[0], dev, torch.float32, what.format("mean_x"), shape=(n, c))
+    sign_mu = _like(state[1], dev, torch.int8, what.format("sign_mu"), shape=(n, c))
+    sign_cov = _like(state[2], dev, torch.int8, what.format("sign_cov"), shape=(n, c, c))
     if grad is not None:
-        grad = _moment_like(grad.reshape(()) if isinstance(grad, torch.Tensor) and grad.numel() == 1 else grad, dev,
-                            (), torch.float32, what.format("grad"))
+        grad = _like(grad.reshape(()) if isinstance(grad, torch.Tensor) and grad.numel() == 1 else grad, dev,
+                     torch.float32, what.format("grad"), shape=())
     if out is not None:
         if not isinstance(out, torch.Tensor) or not out.is_contiguous():
             raise HipOpError("moment_loss_backward: out must be a contiguous tensor")
-        out = _moment_like(out, dev, x.shape, torch.float32, what.format("out"))
+        out = _like(out, dev, torch.float32, what.format("out"), shape=x.shape)
     dx = out if out is not None else torch.empty_like(x)
     check(_timed(f"moment_loss_backward {c}ch {m}", 2 * n * c * c * m, dev, lambda: lib().ast_moment_loss_backward_f32(
         ptr(x), ptr(mean_x), ptr(sign_mu), ptr(sign_cov), ptr(grad), ptr(dx), n, c, m, float(weight),
@@ -1316,26 +1296,17 @@ def _bank_patches(s: int, hs: int, ws: int, what: str) -> int:
 def _swap_bank(a: torch.Tensor, b: torch.Tensor, na: str, nb: str, what: str):
     """Content-side maps a [N, C, H, W] and a style bank b [S, C, Hs, Ws] (fp32, on one device, equal C,
     sides of at least 3, S * (Hs - 2) * (Ws - 2) < 2^31): (a, b, n, S, c, ha, wa, hb, wb)."""
-    a, b = _dev(a, na), _dev(b, nb)
-    if (a.dim() != 4 or b.dim() != 4 or a.shape[1] != b.shape[1] or a.numel() == 0 or b.numel() == 0
-            or min(a.shape[2:]) < 3 or min(b.shape[2:]) < 3):
-        raise HipOpError(f"{what} needs non-empty NCHW maps with equal C and sides of at least 3: "
-                         f"{na} {tuple(a.shape)} vs {nb} {tuple(b.shape)}")
-    if a.device != b.device:
-        raise HipOpError(f"{nb} is on {b.device}, {na} on {a.device}")
-    _bank_patches(b.shape[0], b.shape[2], b.shape[3], what)
-    n, c, ha, wa = (int(s) for s in a.shape)
-    return a, b, n, int(b.shape[0]), c, ha, wa, int(b.shape[2]), int(b.shape[3])
+    a, b, n, s, c, ha, wa, hb, wb = _pair(a, b, na, nb, what, batch=False, side=3)
+    _bank_patches(s, hb, wb, what)
+    return a, b, n, s, c, ha, wa, hb, wb
 
 
 def _swap_classes(cls, shape, device, name):
     """A class map for `shape` patches: None (all 0) or a uint8 tensor of that shape on `device`."""
     if cls is None:
         return torch.zeros(shape, device=device, dtype=torch.uint8)
-    if (not isinstance(cls, torch.Tensor) or cls.dtype != torch.uint8 or tuple(cls.shape) != tuple(shape)
-            or cls.device != device):
-        raise HipOpError(f"{name} must be a uint8 tensor {tuple(shape)} on {device}")
-    return cls.contiguous()
+    return _like(cls, device, torch.uint8, name, shape=shape,
+                 msg=f"{name} must be a uint8 tensor {tuple(shape)} on {device}")
 
 
 def patch_match_guided(content_key: torch.Tensor, style_keys: torch.Tensor, content_class: torch.Tensor,
@@ -1375,10 +1346,8 @@ def patch_gather_guided(style_values: torch.Tensor, index: torch.Tensor, content
     average; a pixel none of whose covering patches has a match is a copy of the content. One launch."""
     c_, sv, n, s, c, hc, wc, hs, ws = _swap_bank(content, style_values, "content_map", "style_values",
                                                  "patch_gather_guided")
-    if (not isinstance(index, torch.Tensor) or index.device != c_.device or index.dtype != torch.int32
-            or tuple(index.shape) != (n, hc - 2, wc - 2)):
-        raise HipOpError(f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
-    index = index.contiguous()
+    index = _like(index, c_.device, torch.int32, "index", shape=(n, hc - 2, wc - 2),
+                  msg=f"index must be an int32 tensor {(n, hc - 2, wc - 2)} on {c_.device}")
     out = torch.empty_like(c_)
     check(_timed(f"patch_gather_guided {c}ch {hc}x{wc}", -4 * 11 * c_.numel(), c_.device,
                  lambda: lib().ast_patch_gather_guided_f32(ptr(sv), ptr(index), ptr(c_), ptr(out), n, s, c, hc, wc, hs,
